@@ -9,11 +9,18 @@ packet array: each rank generates and frames its own slice,
 no collective touches the data path (scaling "weak": fixed work per GPU).
 Rank 0 prints one JSON line.
 
-Measured beside the headline (rank 0, N = 1 only): the other BASELINE
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, print the line.  `--dump-outputs DIR` also writes what the last timed
+step computed (its frames) as DIR/<name>.npy, see dump_outputs().
+
+`--full` measures the rest beside the headline: the timed frames hashed
+against the reference digests, and (rank 0, N = 1 only) the other BASELINE
 shapes as "legs" (1M x 1024, 1M x 64, decode-verify, C4 encode->decode round
 trip, host-memory end to end), a device-to-device copy ceiling, and the
 reference algorithm's CPU path (the oracle's bit-string port of
-utils/packet.py) on a bounded sample on the host cores.
+utils/packet.py) on a bounded sample on the host cores; for N > 1 (or --dist)
+the C5 strong-scaling leg.  `--no-legs` and `--no-cpu-baseline` drop those
+parts of a `--full` run.
 """
 from __future__ import annotations
 
@@ -136,6 +143,42 @@ class Workload:
     def decode(self, batch, i):
         _, _, out = self.sets[i % len(self.sets)]
         return batch.unpack_batch(out, self.layout)
+
+    def frames(self, i):
+        """The frames [n, L + H] that encode(batch, i) wrote."""
+        return self.sets[i % len(self.sets)][2]
+
+
+DUMP_SAMPLE_BYTES = 40_000_000   # of the at most 64 MB a dump may take
+DUMP_SUMS_BYTES = 16_000_000
+DUMP_SEED = 0x5EED0D0F
+
+
+def dump_outputs(torch, frames, path):
+    """What a caller of the timed path received from its last step, as .npy files
+    under `path` (the inputs are a function of the arguments alone, so two
+    builds run with the same arguments can be compared file for file):
+
+    frames_rows.npy  float64 [k]         the rows of the sample, ascending: a seeded
+                                         choice (the same for the same shape) that
+                                         always holds the first and the last row
+    frames.npy       float32 [k, L + H]  those rows' frame bytes
+    frame_sums.npy   float64 [n]         the sum of the bytes of every frame, so each
+                                         packet of the batch is covered (left out when
+                                         n doubles would pass 16 MB)
+    """
+    import numpy as np
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    n, F = frames.shape
+    k = max(2, min(n, DUMP_SAMPLE_BYTES // (4 * F)))
+    rows = np.arange(n) if k >= n else np.union1d(
+        np.random.default_rng(DUMP_SEED).choice(n, size=k - 2, replace=False), [0, n - 1])
+    idx = torch.from_numpy(rows.astype(np.int64)).to(frames.device)
+    np.save(path / "frames_rows.npy", rows.astype(np.float64))
+    np.save(path / "frames.npy", frames.index_select(0, idx).cpu().numpy().astype(np.float32))
+    if n * 8 <= DUMP_SUMS_BYTES:
+        np.save(path / "frame_sums.npy", frames.sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64))
 
 
 def time_events(torch, fn, steps, warmup):
@@ -1154,8 +1197,13 @@ def main():
                     help="strong scaling: split this many packets over the ranks (C5: 16777216)")
     ap.add_argument("--payload", type=int, default=1472)
     ap.add_argument("--layout", default="rudp7", choices=["rudp5", "rudp7"])
-    ap.add_argument("--no-legs", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the reference-digest check of the timed frames, the CPU "
+                         "baseline, the legs (N = 1) or the C5 strong leg (N > 1, --dist)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's frames (rank 0's) as DIR/<name>.npy")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: without the legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline")
     ap.add_argument("--cpu-workers", type=int, default=0,
                     help="CPU baseline processes (0: one per usable CPU, see usable_cpus())")
     ap.add_argument("--cpu-packets", type=int, default=1 << 15,
@@ -1175,6 +1223,8 @@ def main():
     if args.relay_peer:
         relay_peer(args.relay_peer)
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: start torch.distributed.run as a CHILD process
@@ -1188,7 +1238,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         workers = args.cpu_workers or usable_cpus()["usable"]
         cpu = cpu_baseline(args.payload, max(256, args.cpu_packets * 16 // workers), workers)
         cpu["config1_loopback"] = config1_loopback()
@@ -1248,13 +1298,15 @@ def main():
                                           start.elapsed_time(stop))
     kernel_ms = max(rank_kernel_ms)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, w.frames(args.warmup + args.steps - 1), args.dump_outputs)
     # the timed frames against the reference (BASELINE configs 2-4 by payload size), outside the clock
-    head_chk = verify_digests(w, {1024: "C2", 64: "C3", 1472: "C4"}.get(L, ""), first, n)
+    head_chk = verify_digests(w, {1024: "C2", 64: "C3", 1472: "C4"}.get(L, ""), first, n) if args.full else None
     del w
     torch.cuda.empty_cache()
     extra = legs(torch, batch, device, max(10, args.steps // 2)) if (
-        rank == 0 and not distributed and not args.no_legs) else None
-    if distributed and not args.no_legs and not args.total_packets:
+        args.full and rank == 0 and not distributed and not args.no_legs) else None
+    if args.full and distributed and not args.no_legs and not args.total_packets:
         # BASELINE config 5 beside the weak-scaling headline: 16M x 1472 B split
         # over the ranks (strong scaling), same barrier + max-over-ranks clock.
         extra = {"c5_16Mx1472_strong": c5_strong_leg(torch, dist, batch, device, world, rank,
@@ -1274,6 +1326,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": wall_max / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong" if args.total_packets else "weak",

@@ -1,5 +1,5 @@
-"""bench.py's command line without a GPU: the self-launch of N > 1 ranks and the
-compact baseline summary at the end of the JSON line."""
+"""bench.py's command line without a GPU: the self-launch of N > 1 ranks, the files
+--dump-outputs writes, and the compact baseline summary at the end of the JSON line."""
 import json
 import os
 import subprocess
@@ -21,6 +21,33 @@ def test_gpus_n_without_launcher_starts_torch_distributed_run():
     assert "--nproc-per-node=4" in cmd and "--master-addr=127.0.0.1" in cmd
     i = cmd.index(str(REPO / "bench.py"))
     assert cmd[i + 1:i + 5] == ["--gpus", "4", "--steps", "7"]
+
+
+def test_dump_outputs_sample_is_fixed_and_covers_every_frame(tmp_path, monkeypatch):
+    """--dump-outputs' files from a host tensor: float arrays, the same seeded rows
+    every time (first and last among them), their bytes, and every frame's byte sum."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(REPO))
+    import bench
+    n, F = 1000, 23
+    frames = torch.from_numpy(np.random.default_rng(3).integers(0, 256, (n, F), dtype=np.uint8))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 4 * F * 100)
+    bench.dump_outputs(torch, frames, tmp_path / "a")
+    bench.dump_outputs(torch, frames, tmp_path / "b")
+    a = {p.stem: np.load(p) for p in sorted((tmp_path / "a").iterdir())}
+    b = {p.stem: np.load(p) for p in sorted((tmp_path / "b").iterdir())}
+    assert sorted(a) == sorted(b) == ["frame_sums", "frames", "frames_rows"]
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["frames"].dtype == np.float32 and a["frames_rows"].dtype == a["frame_sums"].dtype == np.float64
+    rows = a["frames_rows"].astype(np.int64)
+    assert 2 <= len(rows) <= 100 and rows[0] == 0 and rows[-1] == n - 1 and (np.diff(rows) > 0).all()
+    assert np.array_equal(a["frames"], frames.numpy()[rows].astype(np.float32))
+    assert np.array_equal(a["frame_sums"], frames.numpy().sum(axis=1, dtype=np.int64).astype(np.float64))
+    # a batch that fits is written whole
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 4 * F * n)
+    bench.dump_outputs(torch, frames, tmp_path / "c")
+    assert np.array_equal(np.load(tmp_path / "c" / "frames.npy"), frames.numpy().astype(np.float32))
 
 
 def test_baseline_summary_is_compact_and_last():

@@ -127,7 +127,7 @@ def test_c5_multirank_processes_match_reference(digests, world):
 
 
 def test_bench_launches_its_own_ranks():
-    """`python3 bench.py --gpus 2 --share-device` with no launcher around it starts
+    """`python3 bench.py --gpus 2 --share-device --full` with no launcher around it starts
     torch.distributed.run itself, as a child process (never an exec), and relays
     rank 0's one line: 2 ranks, bit-exact, and the C5 strong leg's chunks against
     the reference digests (2 of the 16 chunks at --c5-packets 2^21)."""
@@ -140,7 +140,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "2", "--share-device", "--steps", "3",
                         "--warmup", "1", "--packets", str(1 << 18), "--c5-packets", str(1 << 21),
-                        "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=110)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

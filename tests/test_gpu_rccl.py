@@ -40,7 +40,7 @@ def test_bench_distributed_path_over_rccl_at_world_1(cuda):
     barrier + MAX clock, kernel times gathered, the C5 strong leg with its
     device all_reduce of digest counts) at N = 1."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--dist", "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline", "--packets", "262144", "--c5-packets", "1048576"],
+                        "--full", "--no-cpu-baseline", "--packets", "262144", "--c5-packets", "1048576"],
                        cwd=REPO, env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

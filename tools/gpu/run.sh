@@ -4,7 +4,7 @@
 #
 #   bash tools/gpu/run.sh tests [extra pytest args]        # pytest -m gpu
 #   bash tools/gpu/run.sh smoke                            # __graft_entry__.smoke()
-#   bash tools/gpu/run.sh bench TAG [bench.py args]        # one bench line -> gpurun_out/bench_TAG.json
+#   bash tools/gpu/run.sh bench TAG [bench.py args]        # one bench line (--full: with the legs) -> $O/bench_TAG.json
 #   bash tools/gpu/run.sh trace TAG PROG [args]            # rocprofv3 kernel trace + stats
 #   bash tools/gpu/run.sh pmc TAG PROG [args]              # FETCH_SIZE and WRITE_SIZE, one pass each
 #   bash tools/gpu/run.sh pmcsq TAG PROG [args]            # 8 SQ counters (wave cycles, waits, VALU/LDS) in one pass

@@ -77,7 +77,7 @@
 extern "C" {
 #endif
 
-#define RUDP_ABI_VERSION 7
+#define RUDP_ABI_VERSION 8
 
 /* Frame layouts: the value is the header length in bytes. */
 #define RUDP_LAYOUT_RUDP5 5 /* reference-exact 5-byte header, checksum sideband */
@@ -104,6 +104,7 @@ extern "C" {
 #define RUDP_ST_PAYLOAD 2u    /* packed: sum(len) != payload_bytes; gathered: payload outside the buffer */
 #define RUDP_ST_FRAMES_CAP 4u /* sum(len) + n*layout > frames_cap */
 #define RUDP_ST_OFFSETS 8u    /* frame_off decreasing, or outside [0, frames_bytes] */
+#define RUDP_ST_PAYLOAD_CAP 16u /* gather: the kept payloads need more than payload_cap bytes */
 
 /* Error codes (negative errno values, HIP errors offset by -1000). */
 #define RUDP_EINVAL (-22)
@@ -250,6 +251,45 @@ RUDP_API int rudp_decode_varlen_utf8(const uint8_t* d_frames, uint64_t frames_by
                             uint16_t* d_seq, uint16_t* d_ack, uint8_t* d_flags, uint8_t* d_ok,
                             uint16_t* d_csum_out_or_null, uint8_t* d_valid_or_null, uint32_t* d_status,
                             int layout, int device, void* hip_stream);
+
+/*
+ * Packed payload copy-out of packed frames (ABI 8): the step the reference's
+ * receive takes after parsing, `buffer + payload` for every accepted datagram
+ * (utils/reliableUDP.py:121, :135-136) -- the message is the payloads of the
+ * accepted frames back to back -- and the inverse of the packed
+ * rudp_encode_varlen: what a relay that drops corrupt or retransmitted
+ * datagrams and re-frames the rest (proxy.py:90-94) feeds the encode.
+ * Sync-free as the *_checked calls: asynchronous on hip_stream, the host
+ * never waits, temporaries come from the stream's set (usable under stream
+ * capture), and *d_status (required) is written once per call, 0 when valid.
+ * Per frame i < n (frames as rudp_decode_varlen_checked takes them):
+ *   rejected  frame_off[i] > frame_off[i+1] or frame_off[i+1] > frames_bytes
+ *             (the decode's per-frame rule, judged whether or not the frame
+ *             is kept): plen[i] = 0, nothing of the frame is read, and
+ *             RUDP_ST_OFFSETS is set;
+ *   dropped   d_keep_or_null[i] == 0 (NULL: every frame kept): plen[i] = 0;
+ *   kept      plen[i] = max(frame length - layout, 0): a frame shorter than
+ *             the header contributes nothing.
+ * d_payload_off[0..n] receives the exclusive scan of plen (d_payload_off[n] =
+ * the total); all n + 1 entries are always written.  When the total exceeds
+ * payload_cap, RUDP_ST_PAYLOAD_CAP is set and no byte of d_payload is written
+ * (the caller reads the size it needs from d_payload_off[n]); otherwise
+ * d_payload[payload_off[i], payload_off[i+1]) is frame i's payload, and
+ * nothing is written outside [0, total) of d_payload: no byte before it and
+ * none from `total` on, even inside payload_cap.  d_payload and
+ * d_payload_off + a u32 len array of their differences are rudp_batch's
+ * packed payload.  d_payload must not overlap d_frames: compaction in place
+ * is not supported.  len_hint: the typical frame length (0 = unknown/tiny),
+ * which picks the tile geometry, never the result; frames of any length the
+ * buffer can hold are gathered.  n == 0 returns 0 and touches nothing.
+ * Totals of 2^53 bytes and more (only overlapping frames can reach them)
+ * are reported as RUDP_ST_PAYLOAD_CAP with d_payload_off unspecified.
+ */
+RUDP_API int rudp_gather_payloads(const uint8_t* d_frames, uint64_t frames_bytes,
+                                  const uint64_t* d_frame_off, uint32_t len_hint, uint64_t n,
+                                  const uint8_t* d_keep_or_null, uint8_t* d_payload,
+                                  uint64_t payload_cap, uint64_t* d_payload_off,
+                                  uint32_t* d_status, int layout, int device, void* hip_stream);
 
 /*
  * Bounds of a variable-length batch, computed on the device (argument checks

@@ -995,6 +995,41 @@ int rudp_frame_off_check(const uint64_t* d_frame_off, uint64_t n, uint64_t frame
   return 0;
 }
 
+int rudp_gather_payloads(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
+                         uint32_t len_hint, uint64_t n, const uint8_t* d_keep_or_null, uint8_t* d_payload,
+                         uint64_t payload_cap, uint64_t* d_payload_off, uint32_t* d_status, int layout, int device,
+                         void* hip_stream) {
+  if (layout != RUDP_LAYOUT_RUDP5 && layout != RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "unsupported layout %d (use 5 or 7)", layout);
+  if (n == 0) return 0;
+  if (!d_status) return fail(RUDP_EINVAL, "rudp_gather_payloads: d_status is NULL");
+  if (!d_frame_off) return fail(RUDP_EINVAL, "rudp_gather_payloads: d_frame_off is NULL");
+  if (!d_payload_off) return fail(RUDP_EINVAL, "rudp_gather_payloads: d_payload_off is NULL");
+  if (!d_frames && frames_bytes) return fail(RUDP_EINVAL, "rudp_gather_payloads: d_frames is NULL");
+  if (!d_payload && payload_cap) return fail(RUDP_EINVAL, "rudp_gather_payloads: d_payload is NULL");
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  GatherArgs a{};
+  // the frames pointer moved back to a 16-B boundary: a tile stages its run
+  // with aligned 16-B loads from any caller alignment
+  a.fmis = reinterpret_cast<uintptr_t>(d_frames) & 15u;
+  a.frames = d_frames - a.fmis;
+  a.frames_bytes = frames_bytes;
+  a.frame_off = d_frame_off;
+  a.keep = d_keep_or_null;
+  a.n = n;
+  a.H = (uint32_t)layout;
+  a.out = d_payload;
+  a.payload_cap = payload_cap;
+  a.payload_off = d_payload_off;
+  a.status = d_status;
+  ScratchCall call((hipStream_t)hip_stream);  // the tile sums, until the last launch
+  rc = launch_gather_payloads(a, len_hint, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "payload gather launch");
+  return 0;
+}
+
 int rudp_varlen_bounds(const uint32_t* d_len, const int64_t* d_payload_off_or_null, uint64_t n,
                        int64_t* h_out, int device, void* hip_stream) {
   if (!h_out) return fail(RUDP_EINVAL, "rudp_varlen_bounds: h_out is NULL");

@@ -215,6 +215,25 @@ struct DedupArgs {
   uint32_t small_cap;         // > 0: the one-launch small-frame form, LDS run budget in bytes
 };
 
+// Packed payload copy-out of packed frames (gather.hip): payload i =
+// frames[frame_off[i] + H, frame_off[i + 1]) of every kept frame, back to back.
+struct GatherArgs {
+  const unsigned char* frames;  // moved back to a 16-B boundary by the launcher
+  uint64_t fmis;                // distance of the caller's frames[0] from it (0..15)
+  uint64_t frames_bytes;        // size of the caller's buffer: the offset rule's limit
+  const uint64_t* frame_off;    // [n + 1]
+  const uint8_t* keep;          // [n], or null: every frame kept
+  uint64_t n;
+  uint32_t H;
+  uint32_t R;                   // frames per tile (a power of two up to 256, or 1024: four per thread)
+  uint32_t cap;                 // small-frame tiles: LDS bytes the frame run may use (a tile past it reads HBM)
+  uint32_t xcd;                 // XCD-contiguous tile order (xcd_tile)
+  unsigned char* out;
+  uint64_t payload_cap;
+  uint64_t* payload_off;        // [n + 1]
+  uint32_t* status;             // written once by the second launch, read by the third
+};
+
 constexpr uint32_t kTileMaxPayload = 4096;
 // Largest payload accepted: a UDP datagram's size field is 16 bits, and it
 // keeps every per-packet word sum exact in 32 bits (32768 words x 0xFFFF).
@@ -513,6 +532,10 @@ int launch_encode_stride_small(const VarlenArgs& args, int layout, hipStream_t s
 // frames[i F + H, (i + 1) F) to out[i L, (i + 1) L), L = F - H (varlen.hip).
 int launch_copy_payloads(const unsigned char* frames, uint32_t F, uint32_t H, uint64_t n, unsigned char* out,
                          hipStream_t stream);
+// Packed payload copy-out of packed frames (gather.hip): fills in the tile
+// geometry (R, cap) from the typical frame length, takes the block sums from
+// the stream's scratch (inside a ScratchCall) and enqueues the three launches.
+int launch_gather_payloads(GatherArgs args, uint32_t len_hint, hipStream_t stream);
 // Span starts for the byte-tiled varlen encode: rec[k] (k = 0 .. count) holds
 // p, the first packet whose packed payload starts at or after k * bytes, and
 // fo = frame_off[p], so a tile has its packet range and frame run from two

@@ -106,6 +106,7 @@ _ST_MESSAGES = (
                          "gathered payloads: payload_off + lengths must stay inside payload"),
     (_native.ST_FRAMES_CAP, "out is too small for the frames (sum(lengths) + N * header bytes)"),
     (_native.ST_OFFSETS, "frame_off must be non-decreasing offsets inside frames"),
+    (_native.ST_PAYLOAD_CAP, "out is too small for the kept payloads"),
 )
 
 
@@ -831,6 +832,131 @@ def unpack_batch_varlen(frames, frame_off, layout: Union[str, int] = "rudp7", *,
         csum.data_ptr() if csum is not None else None, base, base + 2 * n, base + 6 * n, base + 7 * n,
         base + 4 * n, base + 8 * n if utf8 else None, None, H, dev.index or 0, _stream_ptr(stream, dev)))
     res = VarlenDecoded(buf, n, PayloadSpans(frame_off, H), utf8, stream)
+    return res.check() if check else res
+
+
+class GatheredPayloads:
+    """Result of ``gather_payloads``: ``buffer`` (u8, the whole output buffer:
+    the caller's ``out`` or the allocation; its first payload_off[-1] bytes are
+    the kept payloads back to back), ``payload_off`` (int64 [N + 1]: payload i
+    = buffer[payload_off[i]:payload_off[i + 1]], empty for a dropped, rejected
+    or header-only frame), ``status`` (device int32 [1], RUDP_ST_* of the call,
+    0 = valid), ``lengths`` (int32 [N], the differences of ``payload_off``,
+    computed on first use) and ``payload`` (``buffer[:total]``: the message;
+    one synchronization on first use, to read the total).  ``buffer`` and
+    ``lengths`` are ``pack_batch_varlen``'s packed payload and lengths."""
+
+    __slots__ = ("buffer", "_buf", "_n", "_payload_off", "_status", "_lengths", "_payload")
+
+    # one allocation: payload_off (i64 [n + 1]) | status (i32) | pad
+    def __init__(self, buffer, buf, n: int):
+        self.buffer, self._buf, self._n = buffer, buf, n
+        self._payload_off = self._status = self._lengths = self._payload = None
+
+    @property
+    def payload_off(self):
+        if self._payload_off is None:
+            import torch
+            self._payload_off = self._buf[:8 * (self._n + 1)].view(torch.int64)
+        return self._payload_off
+
+    @property
+    def status(self):
+        if self._status is None:
+            import torch
+            at = 8 * (self._n + 1)
+            self._status = self._buf[at:at + 4].view(torch.int32)
+        return self._status
+
+    @property
+    def lengths(self):
+        if self._lengths is None:
+            import torch
+            off = self.payload_off
+            self._lengths = (off[1:] - off[:-1]).to(torch.int32)
+        return self._lengths
+
+    @property
+    def payload(self):
+        if self._payload is None:
+            self._payload = self.buffer[:min(int(self.payload_off[-1].item()), self.buffer.numel())]
+        return self._payload
+
+    def check(self) -> "GatheredPayloads":
+        """Raise ValueError if the device rejected a frame's offsets or found
+        ``out`` too small (then with the byte count it needs); one synchronization."""
+        bits = int(self.status.item())
+        if bits:
+            msgs = [m for b, m in _ST_MESSAGES if bits & b] or [f"status {bits:#x}"]
+            if bits & _native.ST_PAYLOAD_CAP:
+                msgs.append(f"{int(self.payload_off[-1].item())} bytes are needed, out has {self.buffer.numel()}")
+            raise ValueError("; ".join(msgs))
+        return self
+
+
+def keep_mask(decoded, dup=None):
+    """u8 [N]: 1 for the frames the reference's receive would append to its
+    message -- decoded ``ok == 1``, ``valid == 1`` where the decode judged
+    UTF-8 (``utf8=True``), and, with ``dup`` (``detect_retransmissions``),
+    not a retransmission -- for ``gather_payloads(keep=...)``."""
+    import torch
+    m = decoded.ok == _native.OK_GOOD
+    if decoded.valid is not None:
+        m = m & (decoded.valid == 1)
+    if dup is not None:
+        m = m & (dup == 0)
+    return m.to(torch.uint8)
+
+
+def gather_payloads(frames, frame_off, layout: Union[str, int] = "rudp7", *, keep=None, out=None, stream=None,
+                    check: bool = True) -> GatheredPayloads:
+    """The payloads of the kept frames of a packed batch, back to back, with
+    their offsets: the reference receiver's ``buffer + payload`` per accepted
+    datagram (utils/reliableUDP.py:121, :135-136) for a whole batch, and the
+    inverse of the packed ``pack_batch_varlen`` (rudp_gather_payloads).
+
+    Device tensors only: ``frames`` u8 1-D, ``frame_off`` int64 [N + 1] as
+    ``pack_batch_varlen`` returns them, ``keep`` a u8 or bool [N] tensor (0 =
+    drop the frame; None keeps every frame; see ``keep_mask``).  A frame whose
+    pair of offsets is decreasing or past ``frames`` contributes nothing and is
+    never read, as in ``unpack_batch_varlen``.  ``out``: u8 1-D buffer for the
+    payloads; None allocates frames.numel() bytes, an upper bound that needs
+    no device read.  A caller's ``out`` may be smaller: when the kept payloads
+    do not fit, nothing is written to it and the status says so.
+
+    ``check=True`` waits and raises ValueError for rejected offsets or a too
+    small ``out`` (with the byte count needed); ``check=False`` never waits,
+    and the result's ``check()`` raises later.
+    """
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off):
+        raise TypeError("gather_payloads takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    dev = frames.device
+    if dev.type != "cuda":
+        raise ValueError("gather_payloads runs on a HIP device")
+    _dev_check(frames, "frames", torch.uint8, 1, dev)
+    _int_tensor(frame_off, "frame_off", dev, dtypes=(torch.int64,))
+    n = frame_off.shape[0] - 1
+    if n < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    if keep is not None:
+        _int_tensor(keep, "keep", dev, n, dtypes=(torch.uint8, torch.bool))
+    if out is not None:
+        _dev_check(out, "out", torch.uint8, 1, dev)
+    buffer = out if out is not None else frames.new_empty(frames.numel())
+    head = 8 * (n + 1) + 8
+    buf = frames.new_empty(head)
+    base = buf.data_ptr()
+    if n:
+        _native.check(_native.lib().rudp_gather_payloads(
+            frames.data_ptr() if frames.numel() else None, frames.numel(), frame_off.data_ptr(),
+            min(frames.numel() // n, 0xFFFFFFFF), n, keep.data_ptr() if keep is not None else None,
+            buffer.data_ptr() if buffer.numel() else None, buffer.numel(), base, base + 8 * (n + 1), H,
+            dev.index or 0, _stream_ptr(stream, dev)))
+    else:
+        buf.zero_()
+    res = GatheredPayloads(buffer, buf, n)
     return res.check() if check else res
 
 

@@ -1,6 +1,6 @@
 """Run one codec op repeatedly on one shape, for rocprofv3 captures.
 
-usage: python tools/run_kernel.py --op encode|decode|roundtrip|encode_varlen|decode_varlen|utf8|dedup
+usage: python tools/run_kernel.py --op encode|decode|roundtrip|encode_varlen|decode_varlen|utf8|dedup|gather
           [--L 1472] [--n 1048576]
           [--layout rudp7] [--steps 20] [--ragged] [--tune 51=1,52=2]
 Prints the HIP-event time per launch so it can be set beside the profiler's
@@ -57,16 +57,19 @@ def mixed_text_payloads(n, L, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", choices=["encode", "decode", "decode_copy", "roundtrip", "encode_varlen",
-                                     "decode_varlen", "utf8", "dedup"], default="encode",
+                                     "decode_varlen", "utf8", "dedup", "gather"], default="encode",
                     help="utf8: strict UTF-8 check of the fixed-stride frames (bench leg "
                          "utf8_validate_1Mx1472); dedup: the proxy's 500-deep retransmission check "
-                         "over packed frames of L-byte payloads (bench leg proxy_dedup_1M_window500, L = 1)")
+                         "over packed frames of L-byte payloads (bench leg proxy_dedup_1M_window500, L = 1); "
+                         "gather: packed payload copy-out of packed frames (rudp_gather_payloads; "
+                         "--keep-half drops a random half)")
     ap.add_argument("--L", type=int, default=1472)
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--layout", default="rudp7")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--ragged", action="store_true",
                     help="varlen ops: lengths uniform in [0, 2L] (mean L) instead of all L")
+    ap.add_argument("--keep-half", action="store_true", help="gather: keep mask with a random half dropped")
     ap.add_argument("--utf8", action="store_true",
                     help="decode ops: strict UTF-8 of each payload in the same pass (rudp_decode_utf8)")
     ap.add_argument("--text", action="store_true",
@@ -108,7 +111,7 @@ def main():
     del ctypes
 
     vsets = []
-    if args.op.endswith("varlen") or args.op == "dedup":
+    if args.op.endswith("varlen") or args.op in ("dedup", "gather"):
         for tab, pay, fr in sets:
             if args.ragged:
                 g = torch.Generator(device=dev).manual_seed(7)
@@ -123,6 +126,9 @@ def main():
             dec = batch.unpack_batch_varlen(res.frames, res.frame_off, "rudp5" if args.op == "dedup" else args.layout,
                                             csum=res.csum, utf8=args.utf8)
             vsets.append((tab, flat, lens, res, dec))
+    if args.op == "gather":
+        gbuf = torch.empty_like(vsets[0][3].frames)
+        gkeep = (torch.rand(args.n, device=dev) < 0.5).to(torch.uint8) if args.keep_half else None
 
     def step(i):
         if vsets:
@@ -133,6 +139,8 @@ def main():
                 batch.pack_batch_varlen(tab, flat, lens, args.layout, reuse=res, check=False)
             elif args.op == "dedup":
                 batch.detect_retransmissions(res.frames, frame_off=res.frame_off, window=500)
+            elif args.op == "gather":
+                batch.gather_payloads(res.frames, res.frame_off, args.layout, keep=gkeep, out=gbuf, check=False)
             else:
                 batch.unpack_batch_varlen(res.frames, res.frame_off, args.layout, csum=res.csum, reuse=dec,
                                           check=False, utf8=args.utf8)

@@ -105,6 +105,10 @@ extern "C" {
 #define RUDP_ST_FRAMES_CAP 4u /* sum(len) + n*layout > frames_cap */
 #define RUDP_ST_OFFSETS 8u    /* frame_off decreasing, or outside [0, frames_bytes] */
 #define RUDP_ST_PAYLOAD_CAP 16u /* gather: the kept payloads need more than payload_cap bytes */
+#define RUDP_ST_PACKETS_CAP 32u /* segment: the message makes more than max_packets packets */
+
+/* Entry points added within an ABI version, for C callers to test. */
+#define RUDP_HAS_SEGMENT_UTF8 1 /* rudp_segment_utf8 */
 
 /* Error codes (negative errno values, HIP errors offset by -1000). */
 #define RUDP_EINVAL (-22)
@@ -290,6 +294,61 @@ RUDP_API int rudp_gather_payloads(const uint8_t* d_frames, uint64_t frames_bytes
                                   const uint8_t* d_keep_or_null, uint8_t* d_payload,
                                   uint64_t payload_cap, uint64_t* d_payload_off,
                                   uint32_t* d_status, int layout, int device, void* hip_stream);
+
+/*
+ * A UTF-8 message cut into datagrams on the device (added within ABI 8,
+ * RUDP_HAS_SEGMENT_UTF8): the sender's loop of utils/reliableUDP.py:44-60 --
+ * slice k is message[k*PAYLOAD_SIZE : (k+1)*PAYLOAD_SIZE] in *characters*
+ * (:44, :60), seq = ISN + character pointer (:54), ack 0 (:55), SYN on the
+ * first frame (:45, :56-57) and FIN on the last (:46, :58-59); an empty
+ * message is one SYN|FIN frame -- for any characters per datagram.  The
+ * result is the header table and lengths of the packed rudp_batch whose
+ * payload is d_msg itself (payload_off = NULL), as rudp_encode_varlen[_checked]
+ * takes it.  The inverse of rudp_gather_payloads on the sending side.
+ * Sync-free: asynchronous on hip_stream, the host never waits, temporaries
+ * come from the stream's set.
+ *
+ * Characters and packets.  A byte b is a lead byte when (b & 0xC0) != 0x80;
+ * `characters` is the number of lead bytes in d_msg[0, msg_bytes), which for
+ * valid UTF-8 is Python's len(message).  Validity is not judged here
+ * (rudp_validate_utf8 does that).  packets = max(1, ceil(characters /
+ * chunk_chars)).  Packet 0 starts at byte 0, so continuation bytes before the
+ * first lead byte belong to it; packet k >= 1 starts at the lead byte of
+ * character k * chunk_chars; packet k ends where packet k + 1 starts and the
+ * last one at msg_bytes.  A message without a lead byte, the empty one
+ * included, is one packet holding all its bytes.
+ *
+ * Per packet k < packets:
+ *   d_seq[k]   = (isn + k * chunk_chars) mod 2^16 (computed in 64 bits; isn is
+ *                taken mod 2^16, as set_header_field keeps the low 16 bits,
+ *                utils/packet.py:56)
+ *   d_ack[k]   = 0
+ *   d_flags[k] = 0x80 when k == 0, or'ed with 0x20 when k == packets - 1
+ *   d_len[k]   = the packet's bytes
+ *   d_payload_off_or_null[k] = the packet's first byte, and
+ *                d_payload_off[packets] = msg_bytes (when not NULL)
+ * d_count[0] = packets and d_count[1] = characters are always written.
+ * *d_status is the call's status word, final when the call's work on the
+ * stream is done, 0 when valid: RUDP_ST_PACKETS_CAP when packets >
+ * max_packets; RUDP_ST_LEN when a packet exceeds 65535 bytes (only invalid
+ * UTF-8 can: chunk_chars <= 16383 characters of at most 4 bytes).  With a
+ * non-zero status only d_count is specified.  max_packets == 0 is the size
+ * query: the table pointers may be NULL, d_count is written and the status is
+ * RUDP_ST_PACKETS_CAP.  Nothing is ever written at index >= max_packets of
+ * the tables nor at index > max_packets of d_payload_off; entries in
+ * [packets, max_packets) are unspecified.
+ *
+ * RUDP_EINVAL, before any HIP call: chunk_chars outside [1, 16383]; d_count
+ * or d_status NULL; d_msg NULL with msg_bytes > 0; d_seq, d_ack, d_flags or
+ * d_len NULL with max_packets > 0.  An unaligned d_msg is read as unaligned
+ * buffers are everywhere: whole aligned 16-byte blocks from the boundary at
+ * or below its first byte to the one at or above its last.
+ */
+RUDP_API int rudp_segment_utf8(const uint8_t* d_msg, uint64_t msg_bytes, uint32_t chunk_chars,
+                               uint32_t isn, uint64_t max_packets,
+                               uint16_t* d_seq, uint16_t* d_ack, uint8_t* d_flags, uint32_t* d_len,
+                               uint64_t* d_payload_off_or_null, uint64_t* d_count,
+                               uint32_t* d_status, int device, void* hip_stream);
 
 /*
  * Bounds of a variable-length batch, computed on the device (argument checks

@@ -1030,6 +1030,45 @@ int rudp_gather_payloads(const uint8_t* d_frames, uint64_t frames_bytes, const u
   return 0;
 }
 
+int rudp_segment_utf8(const uint8_t* d_msg, uint64_t msg_bytes, uint32_t chunk_chars, uint32_t isn,
+                      uint64_t max_packets, uint16_t* d_seq, uint16_t* d_ack, uint8_t* d_flags, uint32_t* d_len,
+                      uint64_t* d_payload_off_or_null, uint64_t* d_count, uint32_t* d_status, int device,
+                      void* hip_stream) {
+  if (chunk_chars < 1u || chunk_chars > 16383u)
+    return fail(RUDP_EINVAL, "rudp_segment_utf8: chunk_chars %u outside [1, 16383]", chunk_chars);
+  if (!d_count) return fail(RUDP_EINVAL, "rudp_segment_utf8: d_count is NULL");
+  if (!d_status) return fail(RUDP_EINVAL, "rudp_segment_utf8: d_status is NULL");
+  if (!d_msg && msg_bytes) return fail(RUDP_EINVAL, "rudp_segment_utf8: d_msg is NULL");
+  if (max_packets) {
+    if (!d_seq) return fail(RUDP_EINVAL, "rudp_segment_utf8: d_seq is NULL");
+    if (!d_ack) return fail(RUDP_EINVAL, "rudp_segment_utf8: d_ack is NULL");
+    if (!d_flags) return fail(RUDP_EINVAL, "rudp_segment_utf8: d_flags is NULL");
+    if (!d_len) return fail(RUDP_EINVAL, "rudp_segment_utf8: d_len is NULL");
+  }
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  SegmentArgs a{};
+  // the message pointer moved back to a 16-B boundary: every load is an aligned block
+  a.mis = msg_bytes ? reinterpret_cast<uintptr_t>(d_msg) & 15u : 0u;
+  a.msg = msg_bytes ? d_msg - a.mis : nullptr;
+  a.bytes = msg_bytes;
+  a.chunk = chunk_chars;
+  a.isn = isn & 0xFFFFu;
+  a.max_packets = max_packets;
+  a.seq = d_seq;
+  a.ack = d_ack;
+  a.flags = d_flags;
+  a.len = d_len;
+  a.payload_off = max_packets ? d_payload_off_or_null : nullptr;
+  a.count = d_count;
+  a.status = d_status;
+  ScratchCall call((hipStream_t)hip_stream);  // the tile counts and the starts, until the last launch
+  rc = launch_segment_utf8(a, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "message segment launch");
+  return 0;
+}
+
 int rudp_varlen_bounds(const uint32_t* d_len, const int64_t* d_payload_off_or_null, uint64_t n,
                        int64_t* h_out, int device, void* hip_stream) {
   if (!h_out) return fail(RUDP_EINVAL, "rudp_varlen_bounds: h_out is NULL");

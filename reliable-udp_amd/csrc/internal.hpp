@@ -234,6 +234,25 @@ struct GatherArgs {
   uint32_t* status;             // written once by the second launch, read by the third
 };
 
+// A UTF-8 message cut into datagrams of chunk characters (segment.hip).
+struct SegmentArgs {
+  const unsigned char* msg;     // moved back to a 16-B boundary by the C entry point
+  uint64_t mis;                 // distance of the caller's d_msg from it (0..15)
+  uint64_t bytes;               // msg_bytes
+  uint32_t chunk;               // characters per packet (1..16383)
+  uint32_t isn;
+  uint64_t max_packets;         // capacity of the tables
+  uint32_t rounds;              // rounds of 4096 bytes per tile (a multiple of 4; set by the launcher)
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint32_t* len;
+  uint64_t* payload_off;        // [max_packets + 1], or null
+  uint64_t* starts;             // start[k], 1 <= k < packets: payload_off, else scratch (set by the launcher)
+  uint64_t* count;              // {packets, characters}
+  uint32_t* status;             // written by the second launch, read by the later ones (the last may or RUDP_ST_LEN in)
+};
+
 constexpr uint32_t kTileMaxPayload = 4096;
 // Largest payload accepted: a UDP datagram's size field is 16 bits, and it
 // keeps every per-packet word sum exact in 32 bits (32768 words x 0xFFFF).
@@ -419,6 +438,14 @@ struct Tuning {
   // units; 2 byte tiles with tile_T slots.
   RUDP_KNOB(varlen_diag, 0)
 #endif
+  // Message segmenting (segment.hip): rounds of 4096 bytes per tile (1, 2, 4,
+  // 8, 16); 0 = automatic (launch_segment_utf8).
+  RUDP_KNOB(segment_rounds, 0)
+  // Chunks of at most 16 characters: whole rows from the tile pass (the apron
+  // form, 1) or starts and a last pass of differences (0): 1M one-character
+  // datagrams 21.3 -> 16.7 us (ASCII), 19.4 -> 14.9 (1-4-byte characters;
+  // profiles/r08/segment.json).  Larger chunks always take the differences.
+  RUDP_KNOB(segment_apron, 1)
   RUDP_KNOB(host_slots, 3)     // *_host pipeline: device staging slots (2..8)
   RUDP_KNOB(host_stage_mb, 128)  // *_host pipeline: MiB per slot (1M x 1472 B pinned: 33 ms at 128 vs 94 ms at 32)
   RUDP_KNOB(host_min_chunks, 4)  // *_host pipeline: batches over 4 MiB go as at least this many chunks (copy overlap)
@@ -536,6 +563,10 @@ int launch_copy_payloads(const unsigned char* frames, uint32_t F, uint32_t H, ui
 // geometry (R, cap) from the typical frame length, takes the block sums from
 // the stream's scratch (inside a ScratchCall) and enqueues the three launches.
 int launch_gather_payloads(GatherArgs args, uint32_t len_hint, hipStream_t stream);
+// A UTF-8 message cut into datagrams (segment.hip): picks the tile size, takes
+// the tile counts (and, without d_payload_off, the packet starts) from the
+// stream's scratch (inside a ScratchCall) and enqueues the four launches.
+int launch_segment_utf8(SegmentArgs args, hipStream_t stream);
 // Span starts for the byte-tiled varlen encode: rec[k] (k = 0 .. count) holds
 // p, the first packet whose packed payload starts at or after k * bytes, and
 // fo = frame_off[p], so a tile has its packet range and frame run from two

@@ -282,6 +282,8 @@ RUDP_API int rudpx_copy_vpt(const void* src, void* dst, uint64_t n16, int vpt, i
 // 73: *_host varlen decode: per-frame outputs stored by the kernels into pinned host arrays (1) or copied (0).
 // 74: small-frame varlen encode: pass 1's length codes for the framing kernel (1) or len[] again (0).
 // 75: *_host varlen calls of small frames in pinned memory: one zero-copy launch (1) or the slot pipeline (0).
+// 76: message segmenting: rounds of 4096 bytes per tile (0 = automatic).
+// 77: message segmenting, chunks up to 16 characters: the apron form of len (1) or differences (0).
 // (72: a first-round stagger of half the fused decode tiles' workgroups (s_sleep),
 // 0.539 -> 0.540-0.543 ms on multi-byte text, ASCII 0.229 -> 0.231-0.233: removed;
 // profiles/r05/sweeps/utf8_decode_stagger.json.)
@@ -341,7 +343,9 @@ RUDP_API int rudpx_tune(int key, int value) {
             : key == 71 ? &t.host_min_chunks
             : key == 73 ? &t.host_direct_out
             : key == 74 ? &t.varlen_small_nib
-            : key == 75 ? &t.host_zero_copy : nullptr;
+            : key == 75 ? &t.host_zero_copy
+            : key == 76 ? &t.segment_rounds
+            : key == 77 ? &t.segment_apron : nullptr;
   if (!slot) return -22;
   return slot->exchange(value);
 }

@@ -28,6 +28,7 @@ EINVAL, ENOMEM, ENOTSUP, EHIP_BASE = -22, -12, -95, -1000
 ABI_VERSION = 8
 # status bits of the sync-free varlen calls (RUDP_ST_*)
 ST_LEN, ST_PAYLOAD, ST_FRAMES_CAP, ST_OFFSETS, ST_PAYLOAD_CAP = 1, 2, 4, 8, 16
+ST_PACKETS_CAP = 32  # rudp_segment_utf8: more packets than the tables hold
 DUP_BAD_OFFSETS = 2  # rudp_dedup_window_checked: a frame whose offsets were rejected
 
 # Every symbol include/rudp.h declares (checked by tests/test_abi.py).
@@ -41,7 +42,7 @@ EXPORTS = (
     "rudp_decode_utf8", "rudp_decode_varlen_utf8",
     "rudp_dedup_stream_create", "rudp_dedup_stream_push", "rudp_dedup_stream_counts", "rudp_dedup_stream_destroy",
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
-    "rudp_gather_payloads",
+    "rudp_gather_payloads", "rudp_segment_utf8",
 )
 
 
@@ -98,6 +99,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rudp_decode_varlen_utf8": [P, U64, P, U32, U64, P, P, P, P, P, P, P, P, I, I, P],
         "rudp_frame_off_check": [P, U64, U64, P, I, P],
         "rudp_gather_payloads": [P, U64, P, U32, U64, P, P, U64, P, P, I, I, P],
+        "rudp_segment_utf8": [P, U64, U32, U32, U64, P, P, P, P, P, P, P, I, P],
         "rudp_dedup_stream_create": [U32, U32, U32, I, P, ctypes.POINTER(ctypes.c_void_p)],
         "rudp_dedup_stream_push": [P, P, P, U64, P, P],
         "rudp_dedup_stream_counts": [P, P],

@@ -107,6 +107,7 @@ _ST_MESSAGES = (
     (_native.ST_FRAMES_CAP, "out is too small for the frames (sum(lengths) + N * header bytes)"),
     (_native.ST_OFFSETS, "frame_off must be non-decreasing offsets inside frames"),
     (_native.ST_PAYLOAD_CAP, "out is too small for the kept payloads"),
+    (_native.ST_PACKETS_CAP, "the message makes more packets than max_packets"),
 )
 
 
@@ -958,6 +959,213 @@ def gather_payloads(frames, frame_off, layout: Union[str, int] = "rudp7", *, kee
         buf.zero_()
     res = GatheredPayloads(buffer, buf, n)
     return res.check() if check else res
+
+
+# ------------------------------------------------------------ message -> datagrams
+MAX_CHUNK = 16383  # characters per datagram: 4 * 16383 <= 65535 payload bytes
+
+
+class SegmentTable(NamedTuple):
+    """The first n packets of a ``SegmentedMessage``: ``pack_batch_varlen``'s
+    ``headers`` and ``lengths``, and the n + 1 payload offsets."""
+    headers: HeaderTable
+    lengths: Any
+    payload_off: Any
+
+
+class SegmentedMessage:
+    """Result of ``segment_message``: ``payload`` (u8, the message bytes on the
+    device: the packed payload of every packet), ``headers`` (a ``HeaderTable``
+    of the full-capacity seq / ack / flags arrays), ``lengths`` (int32
+    [capacity]), ``payload_off`` (int64 [capacity + 1]) and ``status`` (device
+    int32 [1], RUDP_ST_* of the call, 0 = valid).  Only the first ``count``
+    entries are packets; ``count`` and ``characters`` are read from the device
+    on first use (one synchronization for both), unless the call knew them on
+    the host (a ``str`` message).  ``table(n)`` slices the arrays to n packets.
+
+    All arrays live in one device allocation and are cut out of it on first use.
+    """
+
+    __slots__ = ("payload", "capacity", "_buf", "_known", "_views")
+
+    # one allocation: payload_off (i64 [cap + 1]) | count (i64 [2]) | status (i32) | pad |
+    # lengths (i32 [cap]) | seq (u16 [cap]) | ack (u16 [cap]) | flags (u8 [cap])
+    def __init__(self, payload, buf, capacity: int, known=None):
+        self.payload, self._buf, self.capacity = payload, buf, capacity
+        self._known = known  # (count, characters) when the host knows them
+        self._views = {}
+
+    @staticmethod
+    def layout(cap: int):
+        """Byte offsets of (count, status, lengths, seq, ack, flags, end) in the allocation."""
+        up = lambda x: x + (-x % 16)  # noqa: E731  (every array on a 16-B boundary)
+        at_count = up(8 * (cap + 1))
+        at_len = at_count + 32
+        at_seq = up(at_len + 4 * cap)
+        at_ack = up(at_seq + 2 * cap)
+        at_flags = up(at_ack + 2 * cap)
+        return at_count, at_count + 16, at_len, at_seq, at_ack, at_flags, at_flags + cap
+
+    def _cut(self, name, lo, hi, dtype):
+        v = self._views.get(name)
+        if v is None:
+            v = self._views[name] = self._buf[lo:hi].view(dtype)
+        return v
+
+    @property
+    def payload_off(self):
+        import torch
+        return self._cut("payload_off", 0, 8 * (self.capacity + 1), torch.int64)
+
+    @property
+    def status(self):
+        import torch
+        at = self.layout(self.capacity)[1]
+        return self._cut("status", at, at + 4, torch.int32)
+
+    @property
+    def lengths(self):
+        import torch
+        at = self.layout(self.capacity)[2]
+        return self._cut("lengths", at, at + 4 * self.capacity, torch.int32)
+
+    @property
+    def headers(self) -> HeaderTable:
+        import torch
+        lay, cap = self.layout(self.capacity), self.capacity
+        return HeaderTable(self._cut("seq", lay[3], lay[3] + 2 * cap, torch.uint16),
+                           self._cut("ack", lay[4], lay[4] + 2 * cap, torch.uint16),
+                           self._cut("flags", lay[5], lay[5] + cap, torch.uint8))
+
+    def _counts(self):
+        if self._known is None:
+            import torch
+            at = self.layout(self.capacity)[0]
+            self._known = tuple(self._buf[at:at + 16].view(torch.int64).tolist())
+        return self._known
+
+    @property
+    def count(self) -> int:
+        """Packets the message makes (it may exceed ``capacity``: then the status says so)."""
+        return self._counts()[0]
+
+    @property
+    def characters(self) -> int:
+        """Lead bytes of the message: len(message) for valid UTF-8."""
+        return self._counts()[1]
+
+    def table(self, n: Optional[int] = None) -> SegmentTable:
+        """The arrays sliced to ``n`` packets; None reads ``count``."""
+        if n is None:
+            n = min(self.count, self.capacity)
+        if not 0 <= n <= self.capacity:
+            raise ValueError(f"n = {n} is outside the table's {self.capacity} entries")
+        h = self.headers
+        return SegmentTable(HeaderTable(h.seq[:n], h.ack[:n], h.flags[:n]), self.lengths[:n], self.payload_off[:n + 1])
+
+    def check(self) -> "SegmentedMessage":
+        """Raise ValueError if the device rejected the call (one synchronization)."""
+        bits = int(self.status.item())
+        if bits:
+            msgs = [m for b, m in _ST_MESSAGES if bits & b] or [f"status {bits:#x}"]
+            if bits & _native.ST_PACKETS_CAP:
+                msgs.append(f"{self.count} packets are needed, the table holds {self.capacity}")
+            raise ValueError("; ".join(msgs))
+        return self
+
+
+def _check_chunk(chunk) -> int:
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= MAX_CHUNK:
+        raise ValueError(f"chunk must be an int in [1, {MAX_CHUNK}] characters per datagram, got {chunk!r}")
+    return chunk
+
+
+def segment_message(message, isn: int, *, chunk: int = 1, max_packets: Optional[int] = None, device=None,
+                    stream=None, check: bool = True, reuse: Optional[SegmentedMessage] = None) -> SegmentedMessage:
+    """Cut a message into datagrams of ``chunk`` characters on the device: the
+    header table and lengths the reference's ``send_data`` derives per datagram
+    (utils/reliableUDP.py:44-60: seq = ISN + character pointer, ack 0, SYN on
+    the first and FIN on the last frame, an empty message one SYN|FIN frame),
+    for the whole message in one call (rudp_segment_utf8).
+
+    ``message``: a ``str``, encoded on the host and copied to ``device``
+    (default "cuda"); its packet count max(1, ceil(len(message) / chunk)) is
+    known on the host, so nothing waits.  Or a u8 1-D tensor of UTF-8 bytes on
+    a HIP device: the table then holds ``max_packets`` entries, by default the
+    bound max(1, ceil(numel / chunk)), which is exact for ASCII.  Characters
+    are counted by lead bytes; validity is not judged (``validate_utf8``).
+
+    ``check=True`` waits and raises ValueError when the message makes more
+    packets than the table holds or a packet exceeds 65535 bytes (invalid
+    UTF-8 only); ``check=False`` never waits.  ``reuse``: an earlier result of
+    the same capacity, whose table takes this call's outputs (no allocation).
+    """
+    chunk = _check_chunk(chunk)
+    import torch
+    known = None
+    if isinstance(message, str):
+        dev = torch.device(device if device is not None else "cuda")
+        if dev.type != "cuda":
+            raise ValueError("segment_message runs on a HIP device")
+        raw = message.encode()
+        payload = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev) if raw else \
+            torch.empty(0, dtype=torch.uint8, device=dev)
+        known = (max(1, -(-len(message) // chunk)), len(message))
+        if max_packets is None:
+            max_packets = known[0]
+    elif _is_torch(message):
+        payload = message
+        dev = payload.device
+        if dev.type != "cuda":
+            raise ValueError("segment_message runs on a HIP device")
+        _dev_check(payload, "message", torch.uint8, 1, dev)
+        if device is not None and torch.device(device).type != "cuda":
+            raise ValueError("segment_message runs on a HIP device")
+        if max_packets is None:
+            max_packets = max(1, -(-payload.numel() // chunk))
+    else:
+        raise TypeError("message must be a str or a u8 torch.Tensor on a HIP device")
+    if isinstance(max_packets, bool) or not isinstance(max_packets, int) or max_packets < 0:
+        raise ValueError(f"max_packets must be a non-negative int, got {max_packets!r}")
+    cap = max_packets
+    lay = SegmentedMessage.layout(cap)
+    if reuse is not None:
+        if not isinstance(reuse, SegmentedMessage) or reuse.capacity != cap or reuse._buf.device != dev:
+            raise ValueError("reuse= must be an earlier segment_message result of the same capacity and device")
+        buf = reuse._buf
+    else:
+        buf = payload.new_empty(lay[6])
+    base = buf.data_ptr()
+    tab = cap > 0
+    _native.check(_native.lib().rudp_segment_utf8(
+        payload.data_ptr() if payload.numel() else None, payload.numel(), chunk, int(isn) & 0xFFFFFFFF, cap,
+        base + lay[3] if tab else None, base + lay[4] if tab else None, base + lay[5] if tab else None,
+        base + lay[2] if tab else None, base if tab else None, base + lay[0], base + lay[1],
+        dev.index if dev.index is not None else torch.cuda.current_device(), _stream_ptr(stream, dev)))
+    res = SegmentedMessage(payload, buf, cap, known)
+    return res.check() if check else res
+
+
+def frame_message(message, isn: int, *, chunk: int = 1, layout: Union[str, int] = "rudp5",
+                  want_csum: bool = False, n: Optional[int] = None, max_packets: Optional[int] = None, device=None,
+                  stream=None, check: bool = True) -> VarlenFrames:
+    """The datagrams of a message as the reference's ``send_data`` builds them
+    (utils/reliableUDP.py:44-61), for the whole message: ``segment_message``,
+    then ``pack_batch_varlen`` on its table.  Returns ``VarlenFrames``: frame k
+    is byte-identical to the reference's packet for message pointer k * chunk.
+
+    The frame batch needs the packet count on the host.  For a ``str`` it is
+    known, and with ``n`` the caller gives it (the first ``n`` packets are
+    framed): the call then never waits (with ``check=False``).  For a device
+    tensor without ``n`` the count is read from the device: one
+    synchronization.
+    """
+    H = layout_header_len(layout)
+    seg = segment_message(message, isn, chunk=chunk, max_packets=max_packets, device=device, stream=stream,
+                          check=check)
+    tab = seg.table(n)  # (n None: the count, from the host for a str, else the one device read)
+    return pack_batch_varlen(tab.headers, seg.payload, tab.lengths, H, want_csum=want_csum, stream=stream,
+                             check=check)
 
 
 def validate_utf8(frames, layout: Union[str, int] = "rudp7", *, frame_off=None, stream=None):

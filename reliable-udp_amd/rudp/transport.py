@@ -176,15 +176,20 @@ class ReliableUDP:
         import torch
         from . import batch
         dev = torch.device(self._codec_device)
-        n = len(message) + 1  # k = len(message): the header-only FIN frame a late resend carries
-        k = np.arange(n, dtype=np.int64)
-        seq = ((isn + k) & 0xFFFF).astype(np.uint16)
-        flags = (np.where(k == 0, SYN, 0) | np.where(k >= len(message) - 1, FIN, 0)).astype(np.uint8)
-        lens = np.array([len(c.encode()) for c in message] + [0], dtype=np.int32)
-        payload = np.frombuffer(bytearray(message.encode()), dtype=np.uint8)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-        res = batch.pack_batch_varlen((t(seq), t(np.zeros(n, np.uint16)), t(flags)), t(payload), t(lens),
-                                      "rudp5", want_csum=False)
+        # rows k < len(message) cut on the device (one character each, seq, SYN and FIN
+        # as send_data sets them); an empty message is the one SYN|FIN row
+        seg = batch.segment_message(message, isn, chunk=CHUNK, device=dev, check=False)
+        tab = seg.table()
+        seq, ack, flags, lens = tab.headers.seq, tab.headers.ack, tab.headers.flags, tab.lengths
+        if message:  # k = len(message): the header-only FIN frame a late resend carries
+            def append(col, value, dtype):  # (joined as bytes: every dtype concatenates that way)
+                row = torch.from_numpy(np.array([value], dtype).view(np.uint8)).to(dev)
+                return torch.cat((col.view(torch.uint8), row)).view(col.dtype)
+            seq = append(seq, (isn + len(message)) & 0xFFFF, np.uint16)
+            ack = append(ack, 0, np.uint16)
+            flags = append(flags, FIN, np.uint8)
+            lens = append(lens, 0, np.int32)
+        res = batch.pack_batch_varlen((seq, ack, flags), seg.payload, lens, "rudp5", want_csum=False)
         return res.frames.cpu().numpy().tobytes(), res.frame_off.cpu().tolist()
 
     # ----------------------------------------------------------- receiver

@@ -109,6 +109,7 @@ extern "C" {
 
 /* Entry points added within an ABI version, for C callers to test. */
 #define RUDP_HAS_SEGMENT_UTF8 1 /* rudp_segment_utf8 */
+#define RUDP_HAS_ACCEPT_INORDER 1 /* rudp_payload_chars, rudp_accept_inorder */
 
 /* Error codes (negative errno values, HIP errors offset by -1000). */
 #define RUDP_EINVAL (-22)
@@ -349,6 +350,84 @@ RUDP_API int rudp_segment_utf8(const uint8_t* d_msg, uint64_t msg_bytes, uint32_
                                uint16_t* d_seq, uint16_t* d_ack, uint8_t* d_flags, uint32_t* d_len,
                                uint64_t* d_payload_off_or_null, uint64_t* d_count,
                                uint32_t* d_status, int device, void* hip_stream);
+
+/*
+ * The receiver's decision between decode and gather: which datagrams of a
+ * batch it accepts (added within ABI 8, RUDP_HAS_ACCEPT_INORDER) --
+ * receive_data of utils/reliableUDP.py:116-137, stop-and-wait: a SYN opens a
+ * transfer (:128-132), then only the frame whose seq_num equals ISN +
+ * characters received so far is accepted (:124, :134-136) -- and the ack_num
+ * of the reply send_ack builds for every datagram (:139-146).  Both calls are
+ * sync-free: asynchronous on hip_stream, the host never waits, usable under
+ * stream capture.
+ *
+ * The rule, in absolute sequence space.  The state is expect = ISN +
+ * characters received (an integer that is never reduced mod 2^16), isn, and
+ * live (the receiver has a peer, self.target_addr).  last_isn is the previous
+ * transfer's ISN (self.prev_random_number), constant during one recv(); a
+ * value above 65535 means none.  Per frame i in arrival order, with seq_i,
+ * syn_i = flags & 0x80, fin_i = flags & 0x20, c_i the characters of its
+ * payload and usable_i:
+ *   ignored    !usable_i: nothing changes, no reply.  syn_i && seq_i ==
+ *              last_isn (a repeated SYN, :126): nothing changes, but a reply
+ *              is sent.
+ *   reset      syn_i otherwise: isn = seq_i, expect = seq_i + c_i, live = 1;
+ *              the frame is accepted and the message restarts at this frame.
+ *   in-order   a non-SYN with live && seq_i == expect, compared as integers
+ *              (once expect > 65535 nothing matches, as in the reference):
+ *              the frame is accepted and expect += c_i.
+ *   else       not accepted.
+ * A reply is sent for every usable frame while live is set after the frame;
+ * its ack_num is expect after the frame, mod 2^16.  The first accepted frame
+ * with FIN ends the call's transfer at index `end`; frames after `end` belong
+ * to the next recv() and are not judged.  With live == 0 nothing before the
+ * first reset is accepted or answered (the reference clears its buffer and
+ * sends nothing while target_addr is None, :140-141).
+ *
+ * rudp_payload_chars: d_chars[i] = c_i, the number of lead bytes
+ * ((b & 0xC0) != 0x80, rudp_segment_utf8's definition; Python's len() for
+ * valid UTF-8) of frame i from byte `layout` on.  Packed frames with n + 1
+ * offsets, frames_bytes and len_hint as rudp_gather_payloads takes them: a
+ * frame shorter than the header gives 0; a frame whose pair of offsets is
+ * decreasing or past frames_bytes gives 0 and none of its bytes is read.
+ * len_hint picks the lanes per frame, never the result; frames of any length
+ * the buffer holds are counted (mod 2^32).  An unaligned d_frames is read as
+ * whole aligned 16-byte blocks, as everywhere.  n == 0 returns 0 and touches
+ * nothing.  RUDP_EINVAL before any HIP call: a layout other than 5 or 7;
+ * with n > 0, d_frame_off or d_chars NULL, or d_frames NULL with frames_bytes.
+ *
+ * rudp_accept_inorder: d_seq, d_flags as the decode wrote them, d_chars from
+ * rudp_payload_chars, d_usable_or_null[i] != 0 for a usable frame (NULL: all
+ * usable), d_state_in = {expect, isn, live, 0}.  Outputs, n entries each:
+ *   d_accept[i]    1 when frame i is accepted by the rule
+ *   d_keep[i]      1 when it is accepted, at or after the last reset at or
+ *                  before `end`, and at or before `end`: the keep mask of
+ *                  rudp_gather_payloads for this call's part of the message
+ *   d_reply[i]     1 when a reply is sent for it, d_reply_ack[i] its ack_num
+ *                  (0 where d_reply[i] is 0)
+ * and all four are 0 for i > end.  d_state_out (u64[4], may be d_state_in):
+ * the state after frame `end`, or after all n.  d_info (u64[6]):
+ *   [0] end (n when no accepted frame has FIN)
+ *   [1] the number of accepted frames
+ *   [2] msg_start: the index of the last reset at or before `end` (n when
+ *       there is none: the caller's carried buffer continues)
+ *   [3] the message's characters so far, expect - isn when live, else 0
+ *   [4] first_anomaly: the index where the one-scan form stopped being exact
+ *       and the sequential form took over (n when it never did; see DESIGN)
+ *   [5] 0, reserved
+ * n == 0 copies the state, writes d_info = {0, 0, 0, characters, 0, 0} and
+ * nothing else.  Temporaries come from the stream's set.  RUDP_EINVAL before
+ * any HIP call: d_state_in, d_state_out or d_info NULL; with n > 0, d_seq,
+ * d_flags, d_chars, d_accept, d_keep, d_reply or d_reply_ack NULL.
+ */
+RUDP_API int rudp_payload_chars(const uint8_t* d_frames, uint64_t frames_bytes,
+                                const uint64_t* d_frame_off, uint32_t len_hint, uint64_t n,
+                                uint32_t* d_chars, int layout, int device, void* hip_stream);
+RUDP_API int rudp_accept_inorder(const uint16_t* d_seq, const uint8_t* d_flags, const uint32_t* d_chars,
+                                 const uint8_t* d_usable_or_null, uint64_t n, uint32_t last_isn,
+                                 const uint64_t* d_state_in, uint8_t* d_accept, uint8_t* d_keep,
+                                 uint8_t* d_reply, uint16_t* d_reply_ack, uint64_t* d_state_out,
+                                 uint64_t* d_info, int device, void* hip_stream);
 
 /*
  * Bounds of a variable-length batch, computed on the device (argument checks

@@ -1069,6 +1069,70 @@ int rudp_segment_utf8(const uint8_t* d_msg, uint64_t msg_bytes, uint32_t chunk_c
   return 0;
 }
 
+int rudp_payload_chars(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
+                       uint32_t len_hint, uint64_t n, uint32_t* d_chars, int layout, int device, void* hip_stream) {
+  if (layout != RUDP_LAYOUT_RUDP5 && layout != RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "unsupported layout %d (use 5 or 7)", layout);
+  if (n == 0) return 0;
+  if (!d_frame_off) return fail(RUDP_EINVAL, "rudp_payload_chars: d_frame_off is NULL");
+  if (!d_chars) return fail(RUDP_EINVAL, "rudp_payload_chars: d_chars is NULL");
+  if (!d_frames && frames_bytes) return fail(RUDP_EINVAL, "rudp_payload_chars: d_frames is NULL");
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  CharsArgs a{};
+  // the frames pointer moved back to a 16-B boundary: every load is an aligned block
+  a.fmis = reinterpret_cast<uintptr_t>(d_frames) & 15u;
+  a.frames = d_frames - a.fmis;
+  a.frames_bytes = frames_bytes;
+  a.frame_off = d_frame_off;
+  a.n = n;
+  a.H = (uint32_t)layout;
+  a.chars = d_chars;
+  rc = launch_payload_chars(a, len_hint, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "payload characters launch");
+  return 0;
+}
+
+int rudp_accept_inorder(const uint16_t* d_seq, const uint8_t* d_flags, const uint32_t* d_chars,
+                        const uint8_t* d_usable_or_null, uint64_t n, uint32_t last_isn, const uint64_t* d_state_in,
+                        uint8_t* d_accept, uint8_t* d_keep, uint8_t* d_reply, uint16_t* d_reply_ack,
+                        uint64_t* d_state_out, uint64_t* d_info, int device, void* hip_stream) {
+  if (!d_state_in) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_state_in is NULL");
+  if (!d_state_out) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_state_out is NULL");
+  if (!d_info) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_info is NULL");
+  if (n) {
+    if (!d_seq) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_seq is NULL");
+    if (!d_flags) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_flags is NULL");
+    if (!d_chars) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_chars is NULL");
+    if (!d_accept) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_accept is NULL");
+    if (!d_keep) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_keep is NULL");
+    if (!d_reply) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_reply is NULL");
+    if (!d_reply_ack) return fail(RUDP_EINVAL, "rudp_accept_inorder: d_reply_ack is NULL");
+  }
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  AcceptArgs a{};
+  a.seq = d_seq;
+  a.flags = d_flags;
+  a.chars = d_chars;
+  a.usable = d_usable_or_null;
+  a.n = n;
+  a.last_isn = last_isn;
+  a.state_in = d_state_in;
+  a.state_out = d_state_out;
+  a.accept = d_accept;
+  a.keep = d_keep;
+  a.reply = d_reply;
+  a.reply_ack = d_reply_ack;
+  a.info = d_info;
+  ScratchCall call((hipStream_t)hip_stream);  // the tile pairs, until the last launch
+  rc = launch_accept_inorder(a, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "in-order acceptance launch");
+  return 0;
+}
+
 int rudp_varlen_bounds(const uint32_t* d_len, const int64_t* d_payload_off_or_null, uint64_t n,
                        int64_t* h_out, int device, void* hip_stream) {
   if (!h_out) return fail(RUDP_EINVAL, "rudp_varlen_bounds: h_out is NULL");

@@ -100,6 +100,17 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
   return v;
 }
 
+// Lead bytes of UTF-8, (b & 0xC0) != 0x80: where a character starts.  Bit i of
+// lead4: byte i of the dword leads; bit i of lead_mask16: byte i of the vector.
+__device__ __forceinline__ uint32_t lead4(uint32_t x) {
+  const uint32_t cont = x & ~(x << 1) & 0x80808080u;  // bit 7 set, bit 6 clear
+  const uint32_t m = (cont ^ 0x80808080u) >> 7;       // bit 8 i: byte i leads
+  return (m * 0x01020408u) >> 24;                     // bits 0, 8, 16, 24 -> 24..27 (no two products meet)
+}
+__device__ __forceinline__ uint32_t lead_mask16(u32x4 v) {
+  return lead4(v.x) | lead4(v.y) << 4 | lead4(v.z) << 8 | lead4(v.w) << 12;
+}
+
 // End-around-carry fold of a 32-bit partial sum to 16 bits.
 __device__ __forceinline__ uint32_t fold16(uint32_t s) {
   s = (s & 0xFFFFu) + (s >> 16);

@@ -253,6 +253,36 @@ struct SegmentArgs {
   uint32_t* status;             // written by the second launch, read by the later ones (the last may or RUDP_ST_LEN in)
 };
 
+// Characters (lead bytes) of every frame's payload (accept.hip).
+struct CharsArgs {
+  const unsigned char* frames;  // moved back to a 16-B boundary by the C entry point
+  uint64_t fmis;                // distance of the caller's frames[0] from it (0..15)
+  uint64_t frames_bytes;        // size of the caller's buffer: the offset rule's limit
+  const uint64_t* frame_off;    // [n + 1]
+  uint64_t n;
+  uint32_t H;
+  uint32_t glog;                // log2 lanes per frame (set by the launcher)
+  uint32_t* chars;              // [n]
+};
+
+// The receiver's in-order acceptance of a batch (accept.hip).
+struct AcceptArgs {
+  const uint16_t* seq;
+  const uint8_t* flags;
+  const uint32_t* chars;
+  const uint8_t* usable;        // [n], or null: every frame usable
+  uint64_t n;
+  uint32_t last_isn;            // above 65535: none
+  const uint64_t* state_in;     // {expect, isn, live, 0}
+  uint64_t* state_out;          // may be state_in
+  uint8_t* accept;
+  uint8_t* keep;
+  uint8_t* reply;
+  uint16_t* reply_ack;
+  uint64_t* info;               // [6]
+  uint64_t* hdr;                // more than one tile: the call's scratch (set by the launcher)
+};
+
 constexpr uint32_t kTileMaxPayload = 4096;
 // Largest payload accepted: a UDP datagram's size field is 16 bits, and it
 // keeps every per-packet word sum exact in 32 bits (32768 words x 0xFFFF).
@@ -446,6 +476,11 @@ struct Tuning {
   // datagrams 21.3 -> 16.7 us (ASCII), 19.4 -> 14.9 (1-4-byte characters;
   // profiles/r08/segment.json).  Larger chunks always take the differences.
   RUDP_KNOB(segment_apron, 1)
+  // Characters per payload (accept.hip): log2 lanes per frame (0..6); -1 = from the length hint.
+  RUDP_KNOB(chars_glog, -1)
+  // In-order acceptance of a batch of at most 1024 frames: every step in one
+  // launch (1) or the five launches of larger batches (0).
+  RUDP_KNOB(accept_single, 1)
   RUDP_KNOB(host_slots, 3)     // *_host pipeline: device staging slots (2..8)
   RUDP_KNOB(host_stage_mb, 128)  // *_host pipeline: MiB per slot (1M x 1472 B pinned: 33 ms at 128 vs 94 ms at 32)
   RUDP_KNOB(host_min_chunks, 4)  // *_host pipeline: batches over 4 MiB go as at least this many chunks (copy overlap)
@@ -567,6 +602,13 @@ int launch_gather_payloads(GatherArgs args, uint32_t len_hint, hipStream_t strea
 // the tile counts (and, without d_payload_off, the packet starts) from the
 // stream's scratch (inside a ScratchCall) and enqueues the four launches.
 int launch_segment_utf8(SegmentArgs args, hipStream_t stream);
+// Characters per payload (accept.hip): lanes per frame from the typical frame
+// length, one launch.
+int launch_payload_chars(CharsArgs args, uint32_t len_hint, hipStream_t stream);
+// In-order acceptance (accept.hip): one launch for a batch of at most 1024
+// frames, else five with the tile pairs in the stream's scratch (inside a
+// ScratchCall).
+int launch_accept_inorder(AcceptArgs args, hipStream_t stream);
 // Span starts for the byte-tiled varlen encode: rec[k] (k = 0 .. count) holds
 // p, the first packet whose packed payload starts at or after k * bytes, and
 // fo = frame_off[p], so a tile has its packet range and frame run from two

@@ -44,18 +44,11 @@ constexpr uint32_t kSegTileBytes = 4096;    // a tile: one round (more for long 
 constexpr uint64_t kSegMaxTiles = 16384;    // tiles double up to kSegMaxRounds rounds while there are more
 constexpr uint32_t kSegMaxRounds = 16;
 
-// Bit i: byte i of the dword is a lead byte.
-__device__ __forceinline__ uint32_t seg_lead4(uint32_t x) {
-  const uint32_t cont = x & ~(x << 1) & 0x80808080u;  // bit 7 set, bit 6 clear
-  const uint32_t m = (cont ^ 0x80808080u) >> 7;       // bit 8 i: byte i leads
-  return (m * 0x01020408u) >> 24;                     // bits 0, 8, 16, 24 -> 24..27 (no two products meet)
-}
-
 // Lead mask of the aligned block at byte A of the aligned buffer (A < E =
 // mis + msg_bytes): bit i is byte A + i, bytes outside [mis, E) cleared.
 __device__ __forceinline__ uint32_t seg_lead_mask(const SegmentArgs& a, uint64_t A, uint64_t E) {
   const u32x4 v = *reinterpret_cast<const u32x4*>(a.msg + A);
-  uint32_t m = seg_lead4(v.x) | seg_lead4(v.y) << 4 | seg_lead4(v.z) << 8 | seg_lead4(v.w) << 12;
+  uint32_t m = lead_mask16(v);
   const uint32_t lo = A < a.mis ? (uint32_t)(a.mis - A) : 0u;  // (only block 0)
   const uint32_t hi = E - A < 16u ? (uint32_t)(E - A) : 16u;
   m &= (0xFFFFu >> (16u - hi)) & (0xFFFFu << lo);

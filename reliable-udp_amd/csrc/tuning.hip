@@ -284,6 +284,8 @@ RUDP_API int rudpx_copy_vpt(const void* src, void* dst, uint64_t n16, int vpt, i
 // 75: *_host varlen calls of small frames in pinned memory: one zero-copy launch (1) or the slot pipeline (0).
 // 76: message segmenting: rounds of 4096 bytes per tile (0 = automatic).
 // 77: message segmenting, chunks up to 16 characters: the apron form of len (1) or differences (0).
+// 78: characters per payload: log2 lanes per frame (-1 = from the length hint).
+// 79: in-order acceptance of at most 1024 frames in one launch (1) or five (0).
 // (72: a first-round stagger of half the fused decode tiles' workgroups (s_sleep),
 // 0.539 -> 0.540-0.543 ms on multi-byte text, ASCII 0.229 -> 0.231-0.233: removed;
 // profiles/r05/sweeps/utf8_decode_stagger.json.)
@@ -345,7 +347,9 @@ RUDP_API int rudpx_tune(int key, int value) {
             : key == 74 ? &t.varlen_small_nib
             : key == 75 ? &t.host_zero_copy
             : key == 76 ? &t.segment_rounds
-            : key == 77 ? &t.segment_apron : nullptr;
+            : key == 77 ? &t.segment_apron
+            : key == 78 ? &t.chars_glog
+            : key == 79 ? &t.accept_single : nullptr;
   if (!slot) return -22;
   return slot->exchange(value);
 }

@@ -42,7 +42,7 @@ EXPORTS = (
     "rudp_decode_utf8", "rudp_decode_varlen_utf8",
     "rudp_dedup_stream_create", "rudp_dedup_stream_push", "rudp_dedup_stream_counts", "rudp_dedup_stream_destroy",
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
-    "rudp_gather_payloads", "rudp_segment_utf8",
+    "rudp_gather_payloads", "rudp_segment_utf8", "rudp_payload_chars", "rudp_accept_inorder",
 )
 
 
@@ -100,6 +100,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rudp_frame_off_check": [P, U64, U64, P, I, P],
         "rudp_gather_payloads": [P, U64, P, U32, U64, P, P, U64, P, P, I, I, P],
         "rudp_segment_utf8": [P, U64, U32, U32, U64, P, P, P, P, P, P, P, I, P],
+        "rudp_payload_chars": [P, U64, P, U32, U64, P, I, I, P],
+        "rudp_accept_inorder": [P, P, P, P, U64, U32, P, P, P, P, P, P, P, I, P],
         "rudp_dedup_stream_create": [U32, U32, U32, I, P, ctypes.POINTER(ctypes.c_void_p)],
         "rudp_dedup_stream_push": [P, P, P, U64, P, P],
         "rudp_dedup_stream_counts": [P, P],

@@ -895,13 +895,18 @@ class GatheredPayloads:
         return self
 
 
-def keep_mask(decoded, dup=None):
-    """u8 [N]: 1 for the frames the reference's receive would append to its
-    message -- decoded ``ok == 1``, ``valid == 1`` where the decode judged
-    UTF-8 (``utf8=True``), and, with ``dup`` (``detect_retransmissions``),
-    not a retransmission -- for ``gather_payloads(keep=...)``."""
+def keep_mask(decoded, dup=None, *, unverified: bool = False):
+    """u8 [N]: 1 for the usable frames of a decoded batch -- decoded
+    ``ok == 1``, ``valid == 1`` where the decode judged UTF-8 (``utf8=True``),
+    and, with ``dup`` (``detect_retransmissions``: the proxy's window rule), not
+    a retransmission.  It knows nothing of sequence numbers: these are the
+    frames a receiver can parse, not the ones it accepts (``accept_inorder``
+    decides that, with this mask as ``usable``).  ``unverified``: rudp5 frames
+    decoded without a sideband checksum (``ok == 3``) are usable too."""
     import torch
     m = decoded.ok == _native.OK_GOOD
+    if unverified:
+        m = m | (decoded.ok == _native.OK_UNVERIFIED)
     if decoded.valid is not None:
         m = m & (decoded.valid == 1)
     if dup is not None:
@@ -959,6 +964,264 @@ def gather_payloads(frames, frame_off, layout: Union[str, int] = "rudp7", *, kee
         buf.zero_()
     res = GatheredPayloads(buffer, buf, n)
     return res.check() if check else res
+
+
+# ------------------------------------------------------------ in-order acceptance
+# The launch geometry of csrc/accept.hip, for callers that size batches and for the
+# tests' edge cases (tests/test_accept_api.py holds these to the kernel source).
+ACCEPT_TILE = 1024      # frames per tile of rudp_accept_inorder; a batch up to one tile is one launch
+ACCEPT_BASES = 256      # tiles up to which its bases pass takes one tile per thread
+CHARS_BLOCK = 256       # threads per workgroup of rudp_payload_chars: 256 / lanes frames each
+NO_ISN = 0xFFFFFFFF     # last_isn: no previous transfer
+
+
+def payload_chars_lanes(len_hint: int, H: int) -> int:
+    """Lanes per frame rudp_payload_chars picks for a typical frame length: the
+    fewest, a power of two up to 64, that leave a lane at most four 16-byte
+    blocks (the geometry only; never the result)."""
+    blocks = max(len_hint - H, 0) // 16 + 1
+    lanes = 1
+    while lanes < 64 and blocks > 4 * lanes:
+        lanes *= 2
+    return lanes
+
+
+def payload_chars(frames, frame_off, layout: Union[str, int] = "rudp7", *, stream=None):
+    """int32 [N]: the characters of every frame's payload, counted as lead bytes
+    ((b & 0xC0) != 0x80: Python's len() of the payload for valid UTF-8), for
+    ``accept_inorder`` (rudp_payload_chars).  Device tensors as
+    ``gather_payloads`` takes them; a frame shorter than the header, or one
+    whose offsets are decreasing or past ``frames``, has 0.  Never waits."""
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off):
+        raise TypeError("payload_chars takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    dev = frames.device
+    if dev.type != "cuda":
+        raise ValueError("payload_chars runs on a HIP device")
+    _dev_check(frames, "frames", torch.uint8, 1, dev)
+    _int_tensor(frame_off, "frame_off", dev, dtypes=(torch.int64,))
+    n = frame_off.shape[0] - 1
+    if n < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    chars = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        _native.check(_native.lib().rudp_payload_chars(
+            frames.data_ptr() if frames.numel() else None, frames.numel(), frame_off.data_ptr(),
+            min(frames.numel() // n, 0xFFFFFFFF), n, chars.data_ptr(), H, dev.index or 0,
+            _stream_ptr(stream, dev)))
+    return chars
+
+
+class Accepted:
+    """Result of ``accept_inorder``: ``accept``, ``keep``, ``reply`` (u8 [N])
+    and ``reply_ack`` (u16 [N]) as rudp_accept_inorder defines them, and
+    ``state`` (int64 [4] on the device: expect, isn, live, 0 after the call;
+    pass it as ``state=`` of the next call).  ``end`` (N when no accepted frame
+    had FIN), ``count`` (accepted frames), ``msg_start`` (index of the last
+    reset at or before ``end``, N when there is none), ``characters`` (of the
+    message so far), ``first_anomaly`` and ``fast`` (the one-scan form was
+    exact: ``first_anomaly == N``) are read from the device on first use, one
+    synchronization for all of them; nothing else waits."""
+
+    __slots__ = ("_buf", "_n", "_lay", "_views", "_info")
+
+    def __init__(self, buf, n: int):
+        self._buf, self._n, self._lay = buf, n, Accepted.layout(n)
+        self._views, self._info = {}, None
+
+    @staticmethod
+    def layout(n: int):
+        """Byte offsets in the one allocation: accept | keep | reply (u8 [n]) |
+        reply_ack (u16 [n]) | state (u64 [4]) | info (u64 [6]); then the size."""
+        ack = (3 * n + 1) & ~1
+        state = (ack + 2 * n + 7) & ~7
+        return 0, n, 2 * n, ack, state, state + 32, state + 80
+
+    def _cut(self, name, lo, nbytes, dtype):
+        v = self._views.get(name)
+        if v is None:
+            v = self._buf[lo:lo + nbytes]
+            v = self._views[name] = v if dtype is None else v.view(dtype)
+        return v
+
+    @property
+    def accept(self):
+        return self._cut("accept", self._lay[0], self._n, None)
+
+    @property
+    def keep(self):
+        return self._cut("keep", self._lay[1], self._n, None)
+
+    @property
+    def reply(self):
+        return self._cut("reply", self._lay[2], self._n, None)
+
+    @property
+    def reply_ack(self):
+        import torch
+        return self._cut("reply_ack", self._lay[3], 2 * self._n, torch.uint16)
+
+    @property
+    def state(self):
+        import torch
+        return self._cut("state", self._lay[4], 32, torch.int64)
+
+    @property
+    def info(self):
+        """int64 [6] on the device: end, count, msg_start, characters, first_anomaly, 0."""
+        import torch
+        return self._cut("info", self._lay[5], 48, torch.int64)
+
+    def _host_info(self):
+        if self._info is None:
+            self._info = [int(v) for v in self.info.tolist()]
+        return self._info
+
+    @property
+    def end(self) -> int:
+        return self._host_info()[0]
+
+    @property
+    def count(self) -> int:
+        return self._host_info()[1]
+
+    @property
+    def msg_start(self) -> int:
+        return self._host_info()[2]
+
+    @property
+    def characters(self) -> int:
+        return self._host_info()[3]
+
+    @property
+    def first_anomaly(self) -> int:
+        return self._host_info()[4]
+
+    @property
+    def fast(self) -> bool:
+        return self._host_info()[4] == self._n
+
+    def __len__(self) -> int:
+        return self._n
+
+
+_NO_STATE = {}  # device index -> the all-zero state (no transfer yet, no peer); only ever read
+
+
+def _accept_state(state, dev):
+    import torch
+    if state is None:
+        # One zero tensor per device, made outside any stream capture and complete
+        # before it is first used (the one wait, once per device), so later calls
+        # on any stream, captured ones included, may read it.  A first call inside
+        # a capture gets a tensor of its own, which belongs to that graph.
+        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        zero = _NO_STATE.get(key)
+        if zero is None:
+            zero = torch.zeros(4, dtype=torch.int64, device=dev)
+            if torch.cuda.is_current_stream_capturing():
+                return zero
+            torch.cuda.current_stream(dev).synchronize()
+            _NO_STATE[key] = zero
+        return zero
+    if _is_torch(state):
+        _int_tensor(state, "state", dev, 4, dtypes=(torch.int64,))
+        return state
+    try:
+        expect, isn, live = (int(v) for v in state)
+    except (TypeError, ValueError):
+        raise TypeError("state must be None, (expect, isn, live) or an Accepted.state tensor") from None
+    if expect < 0 or isn < 0:
+        raise ValueError("state: expect and isn must not be negative")
+    return torch.tensor([expect, isn, 1 if live else 0, 0], dtype=torch.int64).to(dev)
+
+
+def _check_last_isn(last_isn) -> int:
+    if last_isn is None:
+        return NO_ISN
+    if isinstance(last_isn, bool) or not isinstance(last_isn, int) or last_isn < 0:
+        raise ValueError(f"last_isn must be None or a non-negative int, got {last_isn!r}")
+    return min(last_isn, NO_ISN)
+
+
+def accept_inorder(seq, flags, chars, *, usable=None, state=None, last_isn=None, stream=None) -> Accepted:
+    """Which datagrams of a batch the reference's receiver accepts, in arrival
+    order (``receive_data``, utils/reliableUDP.py:116-137: a SYN opens a
+    transfer, then only the frame whose seq_num is ISN + characters received so
+    far is accepted), and the ack_num of the reply it sends for each
+    (``send_ack``, :139-146), on the device with no host wait
+    (rudp_accept_inorder; include/rudp.h states the rule).
+
+    ``seq`` (u16 [N]) and ``flags`` (u8 [N]) as the decode returns them,
+    ``chars`` (int32 [N]) from ``payload_chars``, ``usable`` a u8 or bool [N]
+    tensor (``keep_mask``; None: every frame).  ``state``: None (no transfer
+    yet, no peer), ``(expect, isn, live)``, or the ``state`` of the previous
+    call's result, which carries a transfer across batches without a host
+    read.  (The first ``state=None`` call on a device waits once for its zero
+    state to be written; no later call waits.)  ``last_isn``: the previous transfer's ISN, whose repeated SYN is
+    ignored (None: there was none)."""
+    if not _is_torch(seq) or not _is_torch(flags) or not _is_torch(chars):
+        raise TypeError("accept_inorder takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    dev = seq.device
+    if dev.type != "cuda":
+        raise ValueError("accept_inorder runs on a HIP device")
+    _dev_check(seq, "seq", torch.uint16, 1, dev)
+    n = seq.shape[0]
+    _int_tensor(flags, "flags", dev, n, dtypes=(torch.uint8,))
+    _int_tensor(chars, "chars", dev, n, dtypes=(torch.int32,))
+    if usable is not None:
+        _int_tensor(usable, "usable", dev, n, dtypes=(torch.uint8, torch.bool))
+    last = _check_last_isn(last_isn)
+    st = _accept_state(state, dev)
+    lay = Accepted.layout(n)
+    buf = torch.empty(lay[6], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+    tab = n > 0
+    _native.check(_native.lib().rudp_accept_inorder(
+        seq.data_ptr() if tab else None, flags.data_ptr() if tab else None, chars.data_ptr() if tab else None,
+        usable.data_ptr() if usable is not None and tab else None, n, last, st.data_ptr(),
+        base + lay[0] if tab else None, base + lay[1] if tab else None, base + lay[2] if tab else None,
+        base + lay[3] if tab else None, base + lay[4], base + lay[5], dev.index or 0, _stream_ptr(stream, dev)))
+    return Accepted(buf, n)
+
+
+class ReceivedBatch(NamedTuple):
+    """Result of ``receive_batch``: ``message`` (``GatheredPayloads``: its
+    ``payload`` is this batch's part of the message, the bytes ``recv()``
+    appends), ``accepted`` (``Accepted``) and ``replies`` (``HeaderTable`` of
+    N rows for ``pack_batch``: seq 0, ack = reply_ack, flags ACK where a reply
+    is sent and 0 where none is; select the rows with ``accepted.reply``)."""
+    message: GatheredPayloads
+    accepted: Accepted
+    replies: HeaderTable
+
+
+def receive_batch(frames, frame_off, layout: Union[str, int] = "rudp7", *, csum=None, state=None,
+                  last_isn=None) -> ReceivedBatch:
+    """A batch of datagrams (packed frames, as recvmmsg leaves them) turned into
+    what the reference's ``recv()`` loop makes of them, with no host wait in
+    between, on the current stream: ``unpack_batch_varlen(utf8=True)`` -> ``keep_mask`` (the usable
+    frames; rudp5 without ``csum`` has no checksum to fail) -> ``payload_chars``
+    -> ``accept_inorder`` -> ``gather_payloads(keep=accepted.keep)``.
+
+    ``state`` and ``last_isn`` as ``accept_inorder`` takes them.  When
+    ``accepted.msg_start`` is N the bytes continue the caller's buffer of the
+    earlier batches, else they replace it; ``accepted.end < N`` ends the
+    transfer, and the frames behind it belong to the next call."""
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off):
+        raise TypeError("receive_batch takes torch tensors on a HIP device (no host-memory form)")
+    last = _check_last_isn(last_isn)
+    dec = unpack_batch_varlen(frames, frame_off, H, csum=csum, check=False, utf8=True)
+    usable = keep_mask(dec, unverified=H == 5 and csum is None)
+    chars = payload_chars(frames, frame_off, H)
+    acc = accept_inorder(dec.seq, dec.flags, chars, usable=usable, state=state, last_isn=last)
+    msg = gather_payloads(frames, frame_off, H, keep=acc.keep, check=False)
+    import torch
+    replies = HeaderTable(torch.zeros_like(acc.reply_ack), acc.reply_ack, acc.reply * ACK)
+    return ReceivedBatch(msg, acc, replies)
 
 
 # ------------------------------------------------------------ message -> datagrams

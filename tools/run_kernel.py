@@ -1,6 +1,6 @@
 """Run one codec op repeatedly on one shape, for rocprofv3 captures.
 
-usage: python tools/run_kernel.py --op encode|decode|roundtrip|encode_varlen|decode_varlen|utf8|dedup|gather
+usage: python tools/run_kernel.py --op encode|decode|roundtrip|encode_varlen|decode_varlen|utf8|dedup|gather|chars|accept
           [--L 1472] [--n 1048576]
           [--layout rudp7] [--steps 20] [--ragged] [--tune 51=1,52=2]
 Prints the HIP-event time per launch so it can be set beside the profiler's
@@ -57,12 +57,14 @@ def mixed_text_payloads(n, L, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", choices=["encode", "decode", "decode_copy", "roundtrip", "encode_varlen",
-                                     "decode_varlen", "utf8", "dedup", "gather"], default="encode",
+                                     "decode_varlen", "utf8", "dedup", "gather", "chars", "accept"], default="encode",
                     help="utf8: strict UTF-8 check of the fixed-stride frames (bench leg "
                          "utf8_validate_1Mx1472); dedup: the proxy's 500-deep retransmission check "
                          "over packed frames of L-byte payloads (bench leg proxy_dedup_1M_window500, L = 1); "
                          "gather: packed payload copy-out of packed frames (rudp_gather_payloads; "
-                         "--keep-half drops a random half)")
+                         "--keep-half drops a random half); chars: characters per payload of packed "
+                         "frames (rudp_payload_chars); accept: the receiver's in-order acceptance over "
+                         "the decoded table of those frames (rudp_accept_inorder)")
     ap.add_argument("--L", type=int, default=1472)
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--layout", default="rudp7")
@@ -111,7 +113,7 @@ def main():
     del ctypes
 
     vsets = []
-    if args.op.endswith("varlen") or args.op in ("dedup", "gather"):
+    if args.op.endswith("varlen") or args.op in ("dedup", "gather", "chars", "accept"):
         for tab, pay, fr in sets:
             if args.ragged:
                 g = torch.Generator(device=dev).manual_seed(7)
@@ -130,6 +132,9 @@ def main():
         gbuf = torch.empty_like(vsets[0][3].frames)
         gkeep = (torch.rand(args.n, device=dev) < 0.5).to(torch.uint8) if args.keep_half else None
 
+    if args.op == "accept":
+        achars = [batch.payload_chars(v[3].frames, v[3].frame_off, args.layout) for v in vsets]
+
     def step(i):
         if vsets:
             # the sync-free forms with the outputs reused, as the bench's *_reuse forms:
@@ -139,6 +144,10 @@ def main():
                 batch.pack_batch_varlen(tab, flat, lens, args.layout, reuse=res, check=False)
             elif args.op == "dedup":
                 batch.detect_retransmissions(res.frames, frame_off=res.frame_off, window=500)
+            elif args.op == "chars":
+                batch.payload_chars(res.frames, res.frame_off, args.layout)
+            elif args.op == "accept":
+                batch.accept_inorder(dec.seq, dec.flags, achars[i % nsets])
             elif args.op == "gather":
                 batch.gather_payloads(res.frames, res.frame_off, args.layout, keep=gkeep, out=gbuf, check=False)
             else:

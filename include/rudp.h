@@ -430,6 +430,99 @@ RUDP_API int rudp_accept_inorder(const uint16_t* d_seq, const uint8_t* d_flags, 
                                  uint64_t* d_info, int device, void* hip_stream);
 
 /*
+ * A datagram batch to message and replies in one call (added within ABI 8,
+ * RUDP_HAS_RECEIVE): what the reference's recv() loop makes of the datagrams
+ * of one recvmmsg (utils/reliableUDP.py:97-137) and the send_ack packets it
+ * answers them with (:139-146).  One call does rudp_decode_varlen_utf8, the
+ * usable mask, rudp_payload_chars, rudp_accept_inorder and
+ * rudp_gather_payloads (keep as the mask), every output bit for bit what
+ * those calls write, and builds the reply datagrams.  Sync-free as the
+ * *_checked calls: asynchronous on hip_stream, the host never waits,
+ * temporaries come from the stream's set, usable under stream capture.  A
+ * batch of at most 1024 datagrams in at most 32768 bytes and 261 bytes per
+ * datagram (a recvmmsg batch of this protocol) is one launch of one workgroup
+ * that reads the frames once;
+ * larger batches run the launches of the five calls and a reply builder.
+ *
+ * Inputs: d_frames, frames_bytes, d_frame_off[n + 1], len_hint, n,
+ * d_csum_in_or_null and layout as rudp_decode_varlen_utf8 takes them;
+ * last_isn and d_state_in[4] as rudp_accept_inorder.  Outputs through *out
+ * (device pointers; n entries each unless said otherwise):
+ *   seq, ack, flags, ok, csum_out_or_null, valid
+ *                 as rudp_decode_varlen_utf8 writes them
+ *   usable        u8: 1 when ok is RUDP_OK_GOOD or RUDP_OK_UNVERIFIED and
+ *                 valid == 1.  (RUDP_OK_UNVERIFIED occurs only for layout 5
+ *                 without a sideband checksum, and then for every frame that
+ *                 is long enough.)  A short frame, a frame with a wrong
+ *                 checksum or invalid UTF-8, and a frame with bad offsets
+ *                 (RUDP_OK_BAD_OFFSETS) are not usable.
+ *   chars         u32: rudp_payload_chars' answer
+ *   accept, keep, reply, reply_ack, state_out[4] (may be d_state_in)
+ *                 as rudp_accept_inorder, with `usable` as its mask
+ *   payload, payload_cap, payload_off[n + 1]
+ *                 as rudp_gather_payloads with `keep` as its mask: when the
+ *                 total exceeds payload_cap, RUDP_ST_PAYLOAD_CAP is set, no
+ *                 byte of payload is written and payload_off[n] holds the size
+ *                 needed; nothing is ever written at or past the total
+ *   reply_frames  with R = the number of i with reply[i] == 1: R header-only
+ *                 frames of `layout` bytes at stride `layout`, in arrival
+ *                 order, the k-th being Packet().to_byte() of seq 0, ack =
+ *                 reply_ack[i], flags 0x40 (for layout 7 with the RFC 1071
+ *                 checksum of the header in-band).  The caller provides
+ *                 n * layout bytes; nothing is written at or past R * layout.
+ *   reply_csum_or_null  u16[R]: the checksum of each reply frame (the layout 5
+ *                 sideband; for layout 7 a copy of the in-band value)
+ *   reply_index   u32[R]: the datagram index i of reply k
+ *   reply_peer    u64[R]: the index of the last reset (rudp_accept_inorder's
+ *                 rule) at or before datagram i, or n when this batch has none
+ *                 before it: the datagram whose source address the reply goes
+ *                 to (self.target_addr, :131, :146); n is the peer carried
+ *                 from earlier batches
+ *   info          u64[8]: [0..4] as rudp_accept_inorder's d_info; [5] = R;
+ *                 [6] = the message bytes of this batch (payload_off[n]);
+ *                 [7] = 0, reserved
+ *   status        u32, required: final when the call's work on the stream is
+ *                 done, 0 when valid; RUDP_ST_OFFSETS when any frame was
+ *                 rejected for its offsets, RUDP_ST_PAYLOAD_CAP as above
+ * n == 0 copies the state, writes info (as rudp_accept_inorder's n == 0, with
+ * [5] = [6] = 0) and status = 0, and touches nothing else.
+ * RUDP_EINVAL before any HIP call: out NULL; a layout other than 5 or 7; a
+ * sideband d_csum_in with layout 7; d_state_in, state_out, info or status
+ * NULL; n above 2^32 - 1; with n > 0, d_frame_off or any table other than
+ * csum_out_or_null and reply_csum_or_null NULL, d_frames NULL with
+ * frames_bytes > 0, or payload NULL with payload_cap > 0.
+ */
+#define RUDP_HAS_RECEIVE 1
+typedef struct rudp_received {
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint8_t* ok;
+  uint16_t* csum_out_or_null;
+  uint8_t* valid;
+  uint8_t* usable;
+  uint32_t* chars;
+  uint8_t* accept;
+  uint8_t* keep;
+  uint8_t* reply;
+  uint16_t* reply_ack;
+  uint64_t* state_out;
+  uint8_t* payload;
+  uint64_t payload_cap;
+  uint64_t* payload_off;
+  uint8_t* reply_frames;
+  uint16_t* reply_csum_or_null;
+  uint32_t* reply_index;
+  uint64_t* reply_peer;
+  uint64_t* info;
+  uint32_t* status;
+} rudp_received;
+RUDP_API int rudp_receive(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
+                          uint32_t len_hint, uint64_t n, const uint16_t* d_csum_in_or_null, uint32_t last_isn,
+                          const uint64_t* d_state_in, const rudp_received* out, int layout, int device,
+                          void* hip_stream);
+
+/*
  * Bounds of a variable-length batch, computed on the device (argument checks
  * the varlen entry points need before they can size or trust a buffer; the
  * reference has no batch and so no counterpart).  Synchronous on hip_stream.

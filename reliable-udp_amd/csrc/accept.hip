@@ -34,12 +34,17 @@
 //   5. keep, the count of accepted frames, and zeroes past the end.
 // A batch of one tile (a recvmmsg batch is at most 1024 datagrams) runs the
 // five steps in one launch.
+//
+// receive.hip includes this file with RUDP_ACCEPT_DEVICE_ONLY defined for the
+// device functions of the acceptance alone (its fused kernel judges a tile it
+// decoded into LDS itself): the kernels and launchers below are left out then.
 #include "codec_device.hpp"
 #include "internal.hpp"
 #include "scan_device.hpp"
 
 namespace RUDP_NS {
 
+#ifndef RUDP_ACCEPT_DEVICE_ONLY
 // ------------------------------------------------------------ payload_chars
 
 // G = 1 << glog lanes per frame walk the aligned 16-B blocks of its payload
@@ -93,6 +98,7 @@ int launch_payload_chars(CharsArgs a, uint32_t len_hint, hipStream_t stream) {
   hipLaunchKernelGGL(payload_chars_kernel, dim3((uint32_t)nb), dim3(kBlock), 0, stream, a);
   return (int)hipGetLastError();
 }
+#endif  // RUDP_ACCEPT_DEVICE_ONLY
 
 // ----------------------------------------------------------- accept_inorder
 
@@ -392,37 +398,53 @@ __device__ __forceinline__ void acc_store(const AcceptArgs& a, const AccLds& L, 
   }
 }
 
-// A batch of at most one tile, n == 0 included: every step in one launch.
-__global__ void __launch_bounds__(kBlock) accept_single_kernel(AcceptArgs a) {
-  __shared__ AccLds L;
-  const uint32_t tid = threadIdx.x;
-  const AccSeed seed{a.state_in[0], a.state_in[1], a.state_in[2] ? 1ull : 0ull};
-  if (a.n == 0) {  // (uniform)
-    __syncthreads();  // d_state_out may be d_state_in: every read first
-    if (tid == 0) {
-      a.state_out[0] = seed.expect;
-      a.state_out[1] = seed.isn;
-      a.state_out[2] = seed.live;
-      a.state_out[3] = 0;
-      a.info[0] = a.info[1] = a.info[2] = a.info[4] = a.info[5] = 0;
-      a.info[3] = seed.live ? seed.expect - seed.isn : 0ull;
-    }
-    return;
+// An empty batch: the state copied, d_info for it.
+__device__ __forceinline__ void acc_empty(const AcceptArgs& a, AccSeed seed) {
+  __syncthreads();  // d_state_out may be d_state_in: every read first
+  if (threadIdx.x == 0) {
+    a.state_out[0] = seed.expect;
+    a.state_out[1] = seed.isn;
+    a.state_out[2] = seed.live;
+    a.state_out[3] = 0;
+    a.info[0] = a.info[1] = a.info[2] = a.info[4] = a.info[5] = 0;
+    a.info[3] = seed.live ? seed.expect - seed.isn : 0ull;
   }
+}
+
+// Steps 2 to 5 for a batch of one tile (0 < n <= kAccTile) whose seq, fl, ch
+// and us are in LDS (acc_load, or the fused receive kernel's decode: those
+// four are also at a.seq, a.flags, a.chars and a.usable, which the walk and
+// the finish read) and whose L.e_min, L.a_min and a.info[1] were initialised
+// before the barrier that published them.  Leaves L.end and L.ms set and every
+// output in global memory, visible to the workgroup after a barrier.
+__device__ inline void acc_one_tile(const AcceptArgs& a, AccLds& L, AccSeed seed) {
   const uint32_t Rv = (uint32_t)a.n;
-  if (tid == 0) {
-    L.e_min = a.n;
-    L.a_min = a.n;
-    a.info[1] = 0;
-  }
-  acc_load(a, L, 0, Rv);
-  __syncthreads();
   acc_scan(a, L, 0, Rv, AccP{seed.expect, 0}, seed.live);
   __syncthreads();
   acc_store(a, L, 0, Rv);
   const uint64_t E = L.e_min, A = L.a_min;
   acc_finish(a, L, seed, E, A, nullptr);  // (its barriers order the stores above before step 5's loads)
   acc_final(a, 0, L.end, L.ms, &L.cnt);
+}
+
+#ifndef RUDP_ACCEPT_DEVICE_ONLY
+// A batch of at most one tile, n == 0 included: every step in one launch.
+__global__ void __launch_bounds__(kBlock) accept_single_kernel(AcceptArgs a) {
+  __shared__ AccLds L;
+  const uint32_t tid = threadIdx.x;
+  const AccSeed seed{a.state_in[0], a.state_in[1], a.state_in[2] ? 1ull : 0ull};
+  if (a.n == 0) {  // (uniform)
+    acc_empty(a, seed);
+    return;
+  }
+  if (tid == 0) {
+    L.e_min = a.n;
+    L.a_min = a.n;
+    a.info[1] = 0;
+  }
+  acc_load(a, L, 0, (uint32_t)a.n);
+  __syncthreads();
+  acc_one_tile(a, L, seed);
 }
 
 __global__ void __launch_bounds__(kBlock) accept_join_kernel(AcceptArgs a) {
@@ -518,5 +540,6 @@ int launch_accept_inorder(AcceptArgs a, hipStream_t stream) {
   hipLaunchKernelGGL(accept_final_kernel, dim3((uint32_t)nt), dim3(kBlock), 0, stream, a);
   return (int)hipGetLastError();
 }
+#endif  // RUDP_ACCEPT_DEVICE_ONLY
 
 }  // namespace rudp

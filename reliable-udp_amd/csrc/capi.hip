@@ -1133,6 +1133,99 @@ int rudp_accept_inorder(const uint16_t* d_seq, const uint8_t* d_flags, const uin
   return 0;
 }
 
+int rudp_receive(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off, uint32_t len_hint,
+                 uint64_t n, const uint16_t* d_csum_in_or_null, uint32_t last_isn, const uint64_t* d_state_in,
+                 const rudp_received* out, int layout, int device, void* hip_stream) {
+  if (!out) return fail(RUDP_EINVAL, "rudp_receive: out is NULL");
+  if (layout != RUDP_LAYOUT_RUDP5 && layout != RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "unsupported layout %d (use 5 or 7)", layout);
+  if (d_csum_in_or_null && layout == RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "rudp_receive: d_csum_in with layout 7 (its checksum is in-band)");
+  if (!d_state_in) return fail(RUDP_EINVAL, "rudp_receive: d_state_in is NULL");
+  if (!out->state_out) return fail(RUDP_EINVAL, "rudp_receive: state_out is NULL");
+  if (!out->info) return fail(RUDP_EINVAL, "rudp_receive: info is NULL");
+  if (!out->status) return fail(RUDP_EINVAL, "rudp_receive: status is NULL");
+  if (n > 0xFFFFFFFFull) return fail(RUDP_EINVAL, "rudp_receive: n exceeds 2^32 - 1 (reply_index is 32 bits)");
+  if (n) {
+    if (!d_frame_off) return fail(RUDP_EINVAL, "rudp_receive: d_frame_off is NULL");
+    if (!d_frames && frames_bytes) return fail(RUDP_EINVAL, "rudp_receive: d_frames is NULL");
+    const struct {
+      const void* p;
+      const char* name;
+    } tables[] = {{out->seq, "seq"}, {out->ack, "ack"}, {out->flags, "flags"}, {out->ok, "ok"},
+                  {out->valid, "valid"}, {out->usable, "usable"}, {out->chars, "chars"}, {out->accept, "accept"},
+                  {out->keep, "keep"}, {out->reply, "reply"}, {out->reply_ack, "reply_ack"},
+                  {out->payload_off, "payload_off"}, {out->reply_frames, "reply_frames"},
+                  {out->reply_index, "reply_index"}, {out->reply_peer, "reply_peer"}};
+    for (const auto& t : tables)
+      if (!t.p) return fail(RUDP_EINVAL, "rudp_receive: %s is NULL", t.name);
+    if (!out->payload && out->payload_cap) return fail(RUDP_EINVAL, "rudp_receive: payload is NULL");
+  }
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  ReceiveArgs a{};
+  // the frames pointer moved back to a 16-B boundary: every load is an aligned block
+  a.fmis = reinterpret_cast<uintptr_t>(d_frames) & 15u;
+  a.frames = d_frames - a.fmis;
+  a.frames_bytes = frames_bytes;
+  a.frame_off = d_frame_off;
+  a.csum_in = d_csum_in_or_null;
+  a.n = n;
+  a.H = (uint32_t)layout;
+  a.last_isn = last_isn;
+  a.state_in = d_state_in;
+  a.seq = out->seq;
+  a.ack = out->ack;
+  a.flags = out->flags;
+  a.ok = out->ok;
+  a.csum_out = out->csum_out_or_null;
+  a.valid = out->valid;
+  a.usable = out->usable;
+  a.chars = out->chars;
+  a.accept = out->accept;
+  a.keep = out->keep;
+  a.reply = out->reply;
+  a.reply_ack = out->reply_ack;
+  a.state_out = out->state_out;
+  a.payload = out->payload;
+  a.payload_cap = out->payload_cap;
+  a.payload_off = out->payload_off;
+  a.reply_frames = out->reply_frames;
+  a.reply_csum = out->reply_csum_or_null;
+  a.reply_index = out->reply_index;
+  a.reply_peer = out->reply_peer;
+  a.info = out->info;
+  a.status = out->status;
+  if (receive_fused_ok(n, frames_bytes)) {
+    rc = launch_receive_fused(a, s);
+    if (rc) return hip_fail((hipError_t)rc, "fused receive launch");
+    return 0;
+  }
+  // The chained form: the five calls' launches and the reply builder back to
+  // back on the stream, their temporaries from one set.  The gather writes the
+  // call's status last: its offset rule is the decode's, so RUDP_ST_OFFSETS is
+  // the same bit either way.
+  ScratchCall call(s);
+  rc = rudp_decode_varlen_utf8(d_frames, frames_bytes, d_frame_off, len_hint, n, d_csum_in_or_null, a.seq, a.ack,
+                               a.flags, a.ok, a.csum_out, a.valid, a.status, layout, device, hip_stream);
+  if (rc) return rc;
+  rc = launch_receive_usable(a.ok, a.valid, a.usable, n, s);
+  if (rc) return hip_fail((hipError_t)rc, "usable mask launch");
+  rc = rudp_payload_chars(d_frames, frames_bytes, d_frame_off, len_hint, n, a.chars, layout, device, hip_stream);
+  if (rc) return rc;
+  rc = rudp_accept_inorder(a.seq, a.flags, a.chars, a.usable, n, last_isn, d_state_in, a.accept, a.keep, a.reply,
+                           a.reply_ack, a.state_out, a.info, device, hip_stream);
+  if (rc) return rc;
+  rc = rudp_gather_payloads(d_frames, frames_bytes, d_frame_off, len_hint, n, a.keep, a.payload, a.payload_cap,
+                            a.payload_off, a.status, layout, device, hip_stream);
+  if (rc) return rc;
+  rc = launch_receive_replies(a, s);
+  if (rc) return hip_fail((hipError_t)rc, "reply builder launch");
+  return 0;
+}
+
 int rudp_varlen_bounds(const uint32_t* d_len, const int64_t* d_payload_off_or_null, uint64_t n,
                        int64_t* h_out, int device, void* hip_stream) {
   if (!h_out) return fail(RUDP_EINVAL, "rudp_varlen_bounds: h_out is NULL");

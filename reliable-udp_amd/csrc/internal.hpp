@@ -283,6 +283,43 @@ struct AcceptArgs {
   uint64_t* hdr;                // more than one tile: the call's scratch (set by the launcher)
 };
 
+// A datagram batch to message and replies (receive.hip): the decode's, the
+// acceptance's and the gather's arguments in one, and the reply datagrams.
+struct ReceiveArgs {
+  const unsigned char* frames;  // moved back to a 16-B boundary by the C entry point
+  uint64_t fmis;                // distance of the caller's frames[0] from it (0..15)
+  uint64_t frames_bytes;        // size of the caller's buffer: the offset rule's limit
+  const uint64_t* frame_off;    // [n + 1]
+  const uint16_t* csum_in;      // rudp5 sideband, may be null
+  uint64_t n;
+  uint32_t H;
+  uint32_t last_isn;            // above 65535: none
+  const uint64_t* state_in;     // {expect, isn, live, 0}
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint8_t* ok;
+  uint16_t* csum_out;           // may be null
+  uint8_t* valid;
+  uint8_t* usable;
+  uint32_t* chars;
+  uint8_t* accept;
+  uint8_t* keep;
+  uint8_t* reply;
+  uint16_t* reply_ack;
+  uint64_t* state_out;          // may be state_in
+  unsigned char* payload;
+  uint64_t payload_cap;
+  uint64_t* payload_off;        // [n + 1]
+  unsigned char* reply_frames;  // [n * H]; R * H bytes are written
+  uint16_t* reply_csum;         // [n], may be null
+  uint32_t* reply_index;        // [n]
+  uint64_t* reply_peer;         // [n]
+  uint64_t* info;               // [8]
+  uint32_t* status;
+  uint64_t* tiles;              // chained form: the reply builder's tile pairs (set by the launcher)
+};
+
 constexpr uint32_t kTileMaxPayload = 4096;
 // Largest payload accepted: a UDP datagram's size field is 16 bits, and it
 // keeps every per-packet word sum exact in 32 bits (32768 words x 0xFFFF).
@@ -481,6 +518,10 @@ struct Tuning {
   // In-order acceptance of a batch of at most 1024 frames: every step in one
   // launch (1) or the five launches of larger batches (0).
   RUDP_KNOB(accept_single, 1)
+  // rudp_receive of a batch of at most 1024 frames and kRecvFusedBytes bytes:
+  // the one-workgroup fused kernel (1; 2: also past its mean frame length, for
+  // sweeps) or the chain of the existing launches (0).
+  RUDP_KNOB(receive_fused, 1)
   RUDP_KNOB(host_slots, 3)     // *_host pipeline: device staging slots (2..8)
   RUDP_KNOB(host_stage_mb, 128)  // *_host pipeline: MiB per slot (1M x 1472 B pinned: 33 ms at 128 vs 94 ms at 32)
   RUDP_KNOB(host_min_chunks, 4)  // *_host pipeline: batches over 4 MiB go as at least this many chunks (copy overlap)
@@ -609,6 +650,16 @@ int launch_payload_chars(CharsArgs args, uint32_t len_hint, hipStream_t stream);
 // frames, else five with the tile pairs in the stream's scratch (inside a
 // ScratchCall).
 int launch_accept_inorder(AcceptArgs args, hipStream_t stream);
+// rudp_receive (receive.hip).  The fused form: one workgroup takes the batch
+// from frames to message and replies through LDS; receive_fused_ok says whether
+// a batch takes it (n == 0 always does).  The chained form's two own steps:
+// usable[] from ok[] and valid[], and the reply datagrams from the acceptance's
+// outputs (three launches, the tile pairs in the stream's scratch, inside a
+// ScratchCall; it also completes d_info).
+bool receive_fused_ok(uint64_t n, uint64_t frames_bytes);
+int launch_receive_fused(const ReceiveArgs& args, hipStream_t stream);
+int launch_receive_usable(const uint8_t* ok, const uint8_t* valid, uint8_t* usable, uint64_t n, hipStream_t stream);
+int launch_receive_replies(ReceiveArgs args, hipStream_t stream);
 // Span starts for the byte-tiled varlen encode: rec[k] (k = 0 .. count) holds
 // p, the first packet whose packed payload starts at or after k * bytes, and
 // fo = frame_off[p], so a tile has its packet range and frame run from two

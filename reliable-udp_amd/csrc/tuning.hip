@@ -286,6 +286,8 @@ RUDP_API int rudpx_copy_vpt(const void* src, void* dst, uint64_t n16, int vpt, i
 // 77: message segmenting, chunks up to 16 characters: the apron form of len (1) or differences (0).
 // 78: characters per payload: log2 lanes per frame (-1 = from the length hint).
 // 79: in-order acceptance of at most 1024 frames in one launch (1) or five (0).
+// 80: rudp_receive of at most 1024 frames and kRecvFusedBytes in the fused kernel (1; 2: also past
+//     its mean frame length) or chained (0).
 // (72: a first-round stagger of half the fused decode tiles' workgroups (s_sleep),
 // 0.539 -> 0.540-0.543 ms on multi-byte text, ASCII 0.229 -> 0.231-0.233: removed;
 // profiles/r05/sweeps/utf8_decode_stagger.json.)
@@ -349,7 +351,8 @@ RUDP_API int rudpx_tune(int key, int value) {
             : key == 76 ? &t.segment_rounds
             : key == 77 ? &t.segment_apron
             : key == 78 ? &t.chars_glog
-            : key == 79 ? &t.accept_single : nullptr;
+            : key == 79 ? &t.accept_single
+            : key == 80 ? &t.receive_fused : nullptr;
   if (!slot) return -22;
   return slot->exchange(value);
 }
@@ -382,6 +385,31 @@ RUDP_API int rudpx_copy(const void* src, void* dst, uint64_t n16, uint32_t block
 RUDP_API int rudpx_scratch_stats(int device, uint64_t* out) {
   out[1] = (uint64_t)RUDP_NS::scratch_sets(device);
   return (int)RUDP_NS::pool_used_bytes(device, &out[0]);
+}
+
+// rudp_receive's reply builder alone (the chained form's last three launches),
+// from the tables a receive left in *out: reads seq, flags, usable, reply,
+// reply_ack and payload_off[n]; writes reply_frames, reply_csum, reply_index,
+// reply_peer and info[5..7].  For tools/receive_probe.py.
+RUDP_API int rudpx_receive_replies(const rudp_received* out, uint64_t n, uint32_t last_isn, int layout, void* stream) {
+  if (!out || n == 0 || (layout != 5 && layout != 7)) return -22;
+  RUDP_NS::ReceiveArgs a{};
+  a.n = n;
+  a.H = (uint32_t)layout;
+  a.last_isn = last_isn;
+  a.seq = out->seq;
+  a.flags = out->flags;
+  a.usable = out->usable;
+  a.reply = out->reply;
+  a.reply_ack = out->reply_ack;
+  a.payload_off = out->payload_off;
+  a.reply_frames = out->reply_frames;
+  a.reply_csum = out->reply_csum_or_null;
+  a.reply_index = out->reply_index;
+  a.reply_peer = out->reply_peer;
+  a.info = out->info;
+  RUDP_NS::ScratchCall call((hipStream_t)stream);
+  return RUDP_NS::launch_receive_replies(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -43,6 +43,7 @@ EXPORTS = (
     "rudp_dedup_stream_create", "rudp_dedup_stream_push", "rudp_dedup_stream_counts", "rudp_dedup_stream_destroy",
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
     "rudp_gather_payloads", "rudp_segment_utf8", "rudp_payload_chars", "rudp_accept_inorder",
+    "rudp_receive",
 )
 
 
@@ -59,6 +60,15 @@ class RudpBatch(ctypes.Structure):
         ("len", ctypes.c_void_p),
         ("payload_off", ctypes.c_void_p),
     ]
+
+
+class RudpReceived(ctypes.Structure):
+    """struct rudp_received (include/rudp.h): the output pointers of rudp_receive."""
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "seq", "ack", "flags", "ok", "csum_out", "valid", "usable", "chars", "accept", "keep", "reply",
+        "reply_ack", "state_out", "payload")] + [("payload_cap", ctypes.c_uint64)] + [
+        (name, ctypes.c_void_p) for name in (
+            "payload_off", "reply_frames", "reply_csum", "reply_index", "reply_peer", "info", "status")]
 
 
 class RudpError(RuntimeError):
@@ -102,6 +112,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rudp_segment_utf8": [P, U64, U32, U32, U64, P, P, P, P, P, P, P, I, P],
         "rudp_payload_chars": [P, U64, P, U32, U64, P, I, I, P],
         "rudp_accept_inorder": [P, P, P, P, U64, U32, P, P, P, P, P, P, P, I, P],
+        "rudp_receive": [P, U64, P, U32, U64, P, U32, P, ctypes.POINTER(RudpReceived), I, I, P],
         "rudp_dedup_stream_create": [U32, U32, U32, I, P, ctypes.POINTER(ctypes.c_void_p)],
         "rudp_dedup_stream_push": [P, P, P, U64, P, P],
         "rudp_dedup_stream_counts": [P, P],

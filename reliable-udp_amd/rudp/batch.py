@@ -22,6 +22,7 @@ Layouts:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import threading
 from dataclasses import dataclass
@@ -1222,6 +1223,203 @@ def receive_batch(frames, frame_off, layout: Union[str, int] = "rudp7", *, csum=
     import torch
     replies = HeaderTable(torch.zeros_like(acc.reply_ack), acc.reply_ack, acc.reply * ACK)
     return ReceivedBatch(msg, acc, replies)
+
+
+# ------------------------------------------------------------ batch -> message and replies
+# The geometry of csrc/receive.hip (tests/test_receive_api.py holds these to the source).
+RECV_TILE = ACCEPT_TILE     # a batch of at most this many datagrams ...
+RECV_FUSED_BYTES = 32768    # ... in at most this many bytes ...
+RECV_FUSED_MEAN = 261       # ... and this many per datagram is one launch of one workgroup
+
+
+class Received:
+    """Result of ``receive``: one allocation, every member a view of it.
+
+    ``seq``, ``ack``, ``csum`` (u16 [N]), ``flags``, ``ok``, ``valid`` (u8 [N])
+    as ``unpack_batch_varlen(utf8=True)`` returns them; ``usable`` (u8 [N],
+    ``keep_mask``'s answer) and ``chars`` (int32 [N], ``payload_chars``');
+    ``accepted`` (an ``Accepted``: accept, keep, reply, reply_ack, state and
+    the host reads end, count, msg_start, characters, first_anomaly);
+    ``message`` (a ``GatheredPayloads``: payload, payload_off, lengths,
+    check()); ``reply_frames`` (u8 [N * H]: the first ``reply_count * H`` bytes
+    are the reply datagrams, header-only frames at stride H in arrival order),
+    ``reply_csum`` (u16 [N]), ``reply_index`` (int32 [N]: the datagram each
+    reply answers), ``reply_peer`` (int64 [N]: the datagram whose source the
+    reply goes to, N = the peer carried from earlier batches), of which the
+    first ``reply_count`` entries are written; ``state`` (int64 [4], for the
+    next call's ``state=``), ``info`` (int64 [8]) and ``status`` (int32 [1],
+    RUDP_ST_* of the call) on the device.  ``reply_count``, ``message_bytes``
+    and the host reads of ``accepted`` synchronize once, on first use, and are
+    cached; nothing else waits."""
+
+    __slots__ = ("_buf", "_n", "_H", "_lay", "_views", "_info", "accepted", "message")
+
+    def __init__(self, buf, n: int, H: int, cap: int):
+        self._buf, self._n, self._H, self._lay = buf, n, H, Received.layout(n, H, cap)
+        self._views, self._info = {}, None
+        lay = self._lay
+        self.accepted = Accepted(buf[lay["accepted"]:lay["chars"]], n)
+        self.message = GatheredPayloads(buf[lay["payload"]:lay["payload"] + cap],
+                                        buf[lay["payload_off"]:lay["reply_peer"]], n)
+
+    @staticmethod
+    def layout(n: int, H: int, cap: int):
+        """Byte offsets in the one allocation, every array aligned to its
+        element (the payload to 16 bytes); ``size`` is the allocation's."""
+        lay, at = {}, 0
+        for name, nbytes in (("payload_off", 8 * (n + 1) + 8),           # then status (i32) and a pad
+                             ("reply_peer", 8 * n),
+                             ("accepted", (Accepted.layout(n)[6] + 16 + 7) & ~7),  # its info has 8 words here
+                             ("chars", 4 * n), ("reply_index", 4 * n),
+                             ("seq", 2 * n), ("ack", 2 * n), ("csum", 2 * n), ("reply_csum", 2 * n),
+                             ("flags", n), ("ok", n), ("valid", n), ("usable", n),
+                             ("reply_frames", n * H)):
+            lay[name] = at
+            at += nbytes
+        lay["payload"] = (at + 15) & ~15
+        lay["size"] = lay["payload"] + cap
+        return lay
+
+    def _cut(self, name, nbytes, dtype, at=None):
+        v = self._views.get(name)
+        if v is None:
+            lo = self._lay[name] if at is None else at
+            v = self._buf[lo:lo + nbytes]
+            v = self._views[name] = v if dtype is None else v.view(dtype)
+        return v
+
+    def _u16(self, name):
+        import torch
+        return self._cut(name, 2 * self._n, torch.uint16)
+
+    seq = property(lambda self: self._u16("seq"))
+    ack = property(lambda self: self._u16("ack"))
+    csum = property(lambda self: self._u16("csum"))
+    reply_csum = property(lambda self: self._u16("reply_csum"))
+    flags = property(lambda self: self._cut("flags", self._n, None))
+    ok = property(lambda self: self._cut("ok", self._n, None))
+    valid = property(lambda self: self._cut("valid", self._n, None))
+    usable = property(lambda self: self._cut("usable", self._n, None))
+    reply_frames = property(lambda self: self._cut("reply_frames", self._n * self._H, None))
+
+    @property
+    def chars(self):
+        import torch
+        return self._cut("chars", 4 * self._n, torch.int32)
+
+    @property
+    def reply_index(self):
+        import torch
+        return self._cut("reply_index", 4 * self._n, torch.int32)
+
+    @property
+    def reply_peer(self):
+        import torch
+        return self._cut("reply_peer", 8 * self._n, torch.int64)
+
+    @property
+    def state(self):
+        return self.accepted.state
+
+    @property
+    def info(self):
+        """int64 [8] on the device: end, count, msg_start, characters,
+        first_anomaly, reply_count, message_bytes, 0."""
+        import torch
+        return self._cut("info", 64, torch.int64, self._lay["accepted"] + Accepted.layout(self._n)[5])
+
+    @property
+    def status(self):
+        return self.message.status
+
+    def _host_info(self):
+        if self._info is None:
+            self._info = [int(v) for v in self.info.tolist()]
+            self.accepted._info = self._info[:6]
+        return self._info
+
+    @property
+    def reply_count(self) -> int:
+        return self._host_info()[5]
+
+    @property
+    def message_bytes(self) -> int:
+        return self._host_info()[6]
+
+    def check(self) -> "Received":
+        """Raise ValueError if the device rejected a frame's offsets or the
+        message did not fit; one synchronization."""
+        self.message.check()
+        return self
+
+    def __len__(self) -> int:
+        return self._n
+
+
+def receive(frames, frame_off, layout: Union[str, int] = "rudp7", *, csum=None, state=None, last_isn=None,
+            stream=None) -> Received:
+    """``receive_batch`` and the reply datagrams in one library call
+    (rudp_receive): a batch of datagrams (packed frames, as recvmmsg leaves
+    them) decoded, judged in order and gathered into this batch's part of the
+    message, and the ``send_ack`` packets of utils/reliableUDP.py:139-146 built
+    for ``sendmmsg``, with no host wait and no torch operation in between.  A
+    batch of at most ``RECV_TILE`` datagrams in at most ``RECV_FUSED_BYTES``
+    bytes (and ``RECV_FUSED_MEAN`` per datagram) is one kernel launch.
+
+    ``frames`` (u8 1-D), ``frame_off`` (int64 [N + 1]) and ``csum`` (u16 [N],
+    the rudp5 sideband; None: rudp5 frames are taken unverified) are device
+    tensors; ``state`` and ``last_isn`` as ``accept_inorder`` takes them
+    (``state`` may be the previous result's ``state``, which carries a
+    transfer without a host read).  Every array equals what the calls of
+    ``receive_batch`` return for the same input."""
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off):
+        raise TypeError("receive takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    last = _check_last_isn(last_isn)
+    dev = frames.device
+    if dev.type != "cuda":
+        raise ValueError("receive runs on a HIP device")
+    _dev_check(frames, "frames", torch.uint8, 1, dev)
+    _int_tensor(frame_off, "frame_off", dev, dtypes=(torch.int64,))
+    n = frame_off.shape[0] - 1
+    if n < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    if csum is not None:
+        if H == 7:
+            raise ValueError("rudp7 carries its checksum in-band; csum is for rudp5")
+        _dev_check(csum, "csum", torch.uint16, 1, dev)
+        if csum.shape[0] != n:
+            raise ValueError(f"csum has {csum.shape[0]} entries for {n} frames")
+    st = _accept_state(state, dev)
+    cap = frames.numel()
+    lay = Received.layout(n, H, cap)
+    if n:
+        buf = torch.empty(lay["size"], dtype=torch.uint8, device=dev)
+    else:  # payload_off[0], which an empty call does not write (a few bytes, on the call's stream)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            buf = torch.zeros(lay["size"], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+    alay = Accepted.layout(n)
+    acc = base + lay["accepted"]
+
+    def tab(at):
+        return at if n else None
+
+    out = _native.RudpReceived(
+        seq=tab(base + lay["seq"]), ack=tab(base + lay["ack"]), flags=tab(base + lay["flags"]),
+        ok=tab(base + lay["ok"]), csum_out=tab(base + lay["csum"]), valid=tab(base + lay["valid"]),
+        usable=tab(base + lay["usable"]), chars=tab(base + lay["chars"]), accept=tab(acc + alay[0]),
+        keep=tab(acc + alay[1]), reply=tab(acc + alay[2]), reply_ack=tab(acc + alay[3]), state_out=acc + alay[4],
+        payload=base + lay["payload"] if cap else None, payload_cap=cap, payload_off=tab(base + lay["payload_off"]),
+        reply_frames=tab(base + lay["reply_frames"]), reply_csum=tab(base + lay["reply_csum"]),
+        reply_index=tab(base + lay["reply_index"]), reply_peer=tab(base + lay["reply_peer"]),
+        info=acc + alay[5], status=base + lay["payload_off"] + 8 * (n + 1))
+    _native.check(_native.lib().rudp_receive(
+        frames.data_ptr() if cap else None, cap, frame_off.data_ptr(), min(cap // n, 0xFFFFFFFF) if n else 0, n,
+        csum.data_ptr() if csum is not None and n else None, last, st.data_ptr(), ctypes.byref(out), H,
+        dev.index or 0, _stream_ptr(stream, dev)))
+    return Received(buf, n, H, cap)
 
 
 # ------------------------------------------------------------ message -> datagrams

@@ -225,3 +225,38 @@ class BatchReceiver:
         for t in (d_frames, d_off, dec._buf):  # the decode's outputs are views of one buffer
             t.record_stream(cur)
         return (dec.check() if check else dec), d_frames, d_off
+
+    def receive(self, layout="rudp5", *, csum=None, state=None, last_isn=None, stream=None):
+        """H2D of the received frames as ``decode()`` does it (the same slot and
+        event bookkeeping), then ``batch.receive``: the batch decoded, judged in
+        order and gathered, and its reply datagrams built, in one library call.
+        Never waits for the device.  ``state`` and ``last_isn`` as
+        ``batch.receive`` takes them (the previous result's ``state`` carries a
+        transfer from batch to batch).
+
+        Returns ``(Received, d_frames, d_frame_off)``; reply k goes to
+        ``self.sources[res.reply_peer[k]]`` (``with_sources=True``), or to the
+        peer carried from earlier batches where ``reply_peer[k]`` is the
+        datagram count."""
+        import torch
+        s = stream if stream is not None else self.stream
+        k, n = self._slot, self.count
+        if k < 0:
+            raise RuntimeError("receive() before any recv()")
+        total = int(self._off_t[k][n])
+        s.wait_stream(torch.cuda.current_stream(self.device))  # e.g. csum or state written by the caller
+        with torch.cuda.stream(s):
+            d_frames = torch.empty((total,), dtype=torch.uint8, device=self.device)
+            d_off = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+            d_frames.copy_(self._frames_t[k][:total], non_blocking=True)
+            d_off.copy_(self._off_t[k][:n + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(s)
+            self._copied[k] = ev
+            res = _batch.receive(d_frames, d_off, layout, csum=csum, state=state, last_isn=last_isn, stream=s)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(s)
+        # allocated on `s`, used on the caller's stream from here on
+        for t in (d_frames, d_off, res._buf):  # the result's members are views of one buffer
+            t.record_stream(cur)
+        return res, d_frames, d_off

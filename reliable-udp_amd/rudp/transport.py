@@ -81,11 +81,15 @@ class ReliableUDP:
     PAYLOAD_SIZE = CHUNK
 
     def __init__(self, timeout=1, isn_source: Optional[Callable[[], int]] = None,
-                 codec_device: Optional[str] = None):
+                 codec_device: Optional[str] = None, batch_recv: bool = False):
         self.socket: socket
         self.retransmission_timeout = timeout
         self._draw_isn = isn_source or (lambda: random.randint(1, 5000))
         self._codec_device = codec_device
+        if batch_recv and not codec_device:
+            raise ValueError("batch_recv=True judges the datagrams on the GPU: it needs codec_device")
+        self._batch_recv = batch_recv  # recv() over recvmmsg batches judged on the device (_recv_batches)
+        self._rx: Any = None           # its BatchReceiver, made on first use
         self._last_isn: Optional[int] = None  # the previous transfer's ISN (a repeated SYN is ignored)
         # the sender of the last SYN, kept across recv() calls as the reference
         # keeps self.target_addr (utils/reliableUDP.py:18, :131 only ever set it):
@@ -193,8 +197,53 @@ class ReliableUDP:
         return res.frames.cpu().numpy().tobytes(), res.frame_off.cpu().tolist()
 
     # ----------------------------------------------------------- receiver
+    def _recv_batches(self):
+        """The receive loop of recv() over whole recvmmsg batches: each batch is
+        copied to the device and judged there in one call (batch.receive), its
+        reply datagrams go out with one sendmmsg, and its part of the message
+        joins the buffer.  Returns (isn, text, peer) as the loop below leaves them."""
+        import numpy as np
+        import torch
+        from . import netio
+        if self._rx is None or self._rx.sock is not self.socket:
+            self._rx = netio.BatchReceiver(self.socket, max_msgs=1024, slot_bytes=MAX_DATAGRAM, slots=2,
+                                           device=torch.device(self._codec_device), with_sources=True)
+        rx = self._rx
+        self.socket.setblocking(True)
+        peer = self._peer
+        state = (0, 0, 1 if peer is not None else 0)  # no transfer yet; live: there is someone to answer
+        parts = []
+        while True:
+            n = rx.recv(timeout_ms=-1)
+            if n == 0:
+                continue
+            res, _, _ = rx.receive("rudp5", state=state, last_isn=self._last_isn)
+            state = res.state
+            R = res.reply_count  # (the one wait per batch; every host read below is behind it)
+            acc = res.accepted
+            if R:
+                carried = netio.addr_key(*peer) if peer is not None else 0
+                src = np.append(rx.sources, np.uint64(carried))  # index n: the peer carried from earlier batches
+                dst = src[res.reply_peer[:R].cpu().numpy()]
+                netio.send_batch_to(self.socket, res.reply_frames[:5 * R].cpu().numpy(),
+                                    5 * np.arange(R + 1, dtype=np.int64), dst)
+            if acc.msg_start < n:  # a new transfer started in this batch
+                parts = []
+                peer = netio.key_addr(int(rx.sources[acc.msg_start]))
+                self._peer = peer
+            if peer is None:  # nothing to answer yet: nothing is kept
+                parts = []
+            elif res.message_bytes:
+                parts.append(res.message.payload.cpu().numpy().tobytes())
+            if acc.end < n:
+                break
+        return int(state[1].item()), b"".join(parts).decode(), peer
+
     def recv(self) -> str:
         self.flush_recv_buffer()
+        if self._batch_recv:
+            isn, text, peer = self._recv_batches()
+            return self._finish_recv(isn, text, peer)
         isn, text, peer = 0, "", self._peer
         received = 0  # characters accepted so far (the next in-order frame is isn + received)
         while True:
@@ -216,6 +265,9 @@ class ReliableUDP:
             self.socket.sendto(build(0, isn + len(text), ACK), peer)
             if finished:
                 break
+        return self._finish_recv(isn, text, peer)
+
+    def _finish_recv(self, isn: int, text: str, peer) -> str:
         for _ in range(MAX_SENDS):
             self.socket.sendto(build(0, isn + len(text), FIN | ACK), peer)
             got = self._receive(FIN_WAIT_S)

@@ -31,14 +31,15 @@ def main():
     ap.add_argument("--L", default="1472,1024,64")
     ap.add_argument("--reps", type=int, default=11)
     ap.add_argument("--op", default="encode", choices=["encode", "decode", "varlen", "vdecode", "vu8", "vval", "u8text",
-                                                       "u8ascii", "u8val", "u8valtext"],
+                                                       "u8ascii", "u8val", "u8valtext", "accept"],
                     help="decode: verify-only fixed-length rudp_decode of the encoded frames; varlen: "
                          "rudp_encode_varlen_checked of packed payloads, --L lengths or 'ragged' "
                          "(uniform in [0, 2944]); a 'u' suffix (1472u) times the unchecked rudp_encode_varlen; "
                          "vdecode: rudp_decode_varlen_checked (no status word) of such frames, rudp5 with the "
                          "sideband checksums below 16-B payloads, else rudp7; u8text: rudp_decode_utf8 of "
                          "frames whose payload is valid multi-byte UTF-8 text (1-4 byte characters); u8ascii: "
-                         "rudp_decode_utf8 of the ASCII synthetic frames; u8val / u8valtext: rudp_validate_utf8 (the check alone) of the ASCII / text frames")
+                         "rudp_decode_utf8 of the ASCII synthetic frames; u8val / u8valtext: rudp_validate_utf8 (the check alone) of the ASCII / text frames; accept: rudp_accept_inorder of a "
+                         "clean stop-and-wait stream of --L datagrams (1024: one recvmmsg batch, one launch)")
     args = ap.parse_args()
     _native.lib()  # torch's HIP runtime first
     libs = {}
@@ -76,10 +77,20 @@ def main():
             h.rudp_validate_utf8.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
             h.rudp_validate_utf8.restype = ctypes.c_int
+        if hasattr(h, "rudp_accept_inorder"):
+            h.rudp_accept_inorder.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint64, ctypes.c_uint32] + \
+                [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_void_p]
+            h.rudp_accept_inorder.restype = ctypes.c_int
         libs[name] = h
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream().cuda_stream
     out = {}
+    if args.op == "accept":
+        for spec in args.L.split(","):
+            out[spec] = accept_ab(libs, int(spec), args.reps, dev, stream)
+            print(spec, out[spec], file=sys.stderr, flush=True)
+        print(json.dumps(out, indent=1))
+        return
     if args.op in ("varlen", "vdecode", "vu8", "vval"):
         for spec in args.L.split(","):
             fn = varlen_ab if args.op == "varlen" else vdecode_ab if args.op == "vdecode" else vu8_ab
@@ -246,6 +257,46 @@ def vdecode_ab(libs, spec, reps, dev, stream):
             e.synchronize()
             times[name].append(s.elapsed_time(e) / 10)
     return {"ms": {k: statistics.median(v) for k, v in times.items()}, "exact": exact, "layout": layout}
+
+
+def accept_ab(libs, n, reps, dev, stream):
+    import random
+    sys.path.insert(0, str(REPO / "tests"))
+    import numpy as np
+    from accept_ref import clean_stream
+    seq, flags, chars, usable = (torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(dev)
+                                 for a in clean_stream(random.Random(n), n, p_reset=0.0005, high_isn=0.0))
+    state = torch.zeros(4, dtype=torch.int64, device=dev)
+    # accept | keep | reply (u8 [n]), reply_ack (u16 [n]), state_out (u64 [4]), info (u64 [6]), each 8-B aligned
+    m = (n + 7) & ~7
+    outs = torch.zeros(5 * m + 80, dtype=torch.uint8, device=dev)
+    at = [outs.data_ptr() + k for k in (0, m, 2 * m, 3 * m, 5 * m, 5 * m + 32)]
+    inner = 200 if n <= 4096 else 10
+
+    def call(h):
+        return h.rudp_accept_inorder(seq.data_ptr(), flags.data_ptr(), chars.data_ptr(), usable.data_ptr(), n,
+                                     0xFFFFFFFF, state.data_ptr(), *at, 0, stream)
+    ref, exact = None, {}
+    for name, h in libs.items():
+        outs.zero_()
+        assert call(h) == 0
+        got = outs.clone()
+        ref = got if ref is None else ref
+        exact[name] = bool(torch.equal(got, ref))
+    times = {k: [] for k in libs}
+    for _ in range(reps):
+        for name, h in libs.items():
+            for _ in range(2):
+                call(h)
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(inner):
+                call(h)
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) / inner)
+    return {"ms": {k: statistics.median(v) for k, v in times.items()},
+            "ms_min_max": {k: [min(v), max(v)] for k, v in times.items()}, "exact": exact}
 
 
 def text_flat(lens, dev):

@@ -523,6 +523,124 @@ RUDP_API int rudp_receive(const uint8_t* d_frames, uint64_t frames_bytes, const 
                           void* hip_stream);
 
 /*
+ * The sender's judgement of a reply batch (added within ABI 8,
+ * RUDP_HAS_ACKNOWLEDGE): wait_ack of utils/reliableUDP.py:64-85 for every
+ * reply datagram of one recvmmsg, and the closing packet of send_ack (:87-93).
+ * Both calls are sync-free: asynchronous on hip_stream, the host never waits,
+ * temporaries come from the stream's set, usable under stream capture.
+ *
+ * The rule.  Constants of one send(): isn (self.random_number, at most 65535),
+ * T = total_chars (len(message)), C = chunk_chars (PAYLOAD_SIZE).  State, u64[4]
+ * {p, L, last, done}: p characters acknowledged (self.message_pointer), L the
+ * characters of the outstanding frame (payload_length), last != 0 when that
+ * frame is the message's last (is_last), done.  A fresh transfer starts at
+ * p = 0, L = min(C, T), last = (L == T), done = 0.  Per reply i in arrival
+ * order, with seq_i, ack_i, flags_i and usable_i:
+ *   expected = isn + p + L, an integer that is never reduced mod 2^16;
+ *   valid_i  = usable_i && ack_i == expected (RUDP_ACK_EXACT, :71; once
+ *              expected > 65535 nothing matches, as in the reference);
+ *   !valid_i: nothing changes (:75-76).  Otherwise:
+ *   flags_i & 0x40 (ACK): p = ack_i - isn (:77-78);
+ *   flags_i & 0x20 (FIN): end = i, done = 1, and the call's judging stops; the
+ *              closing datagram has seq = (isn + p) mod 2^16, ack = (seq_i + 1)
+ *              mod 2^16 and flags 0x40 (:79-80, :87-93);
+ *   else last: L = 0 (everything is sent: wait for the FIN at isn + p, :81-82);
+ *   else:      L = min(C, T - p), last = (p + L == T) (:83, :44-46).
+ * Kept from the reference on purpose: a valid reply without the ACK flag does
+ * not advance p, and if it answered the last frame L still drops to 0; the
+ * host's timeout (SEND_DATA) is what recomputes L and last from p.  Replies
+ * after `end` are not judged, and with done set on entry none is: d_valid and
+ * d_pointer are then all 0, end = n and the state is copied.
+ * RUDP_ACK_CUMULATIVE (defined by this library, as the checksum is; the
+ * reference never has two frames in flight) changes valid_i alone:
+ *   valid_i = usable_i && expected <= ack_i <= isn + sent_chars &&
+ *             ((ack_i - isn) % C == 0 || ack_i - isn == T)
+ * where sent_chars (>= p + L, <= T) is what the host has sent so far; a sender
+ * with several frames in flight that lost a reply takes the next one.
+ *
+ * rudp_ack_progress: the rule over decoded tables.  d_ack, d_flags as the
+ * decode wrote them, d_usable_or_null[i] != 0 for a usable reply (NULL: all
+ * usable); d_seq is checked like them and not read (the rule does not depend
+ * on it; the closing datagram's ack_num is d_seq[end] + 1).  Outputs:
+ *   d_valid[i]    u8: valid_i
+ *   d_pointer[i]  u64: p after reply i
+ * and both are 0 for i > end.  d_state_out (u64[4], may be d_state_in): the
+ * state after reply `end`, or after all n.  d_info (u64[8]):
+ *   [0] end (n when no valid reply has FIN)
+ *   [1] the number of valid replies
+ *   [2] characters newly acknowledged (p after - p before)
+ *   [3] p after
+ *   [4] first_anomaly: the index where the one-scan form stopped being exact
+ *       and the sequential form took over (n when it never did; see DESIGN)
+ *   [5] the next frame index ceil(p / C): the row of rudp_segment_utf8's table
+ *       to send next (for p == T > 0 the header-only FIN row a caller appends)
+ *   [6] done
+ *   [7] 0, reserved
+ * n == 0 copies the state, writes d_info and nothing else.  RUDP_EINVAL before
+ * any HIP call: d_state_in, d_state_out or d_info NULL; isn above 65535;
+ * chunk_chars outside [1, 16383]; a mode other than the two; sent_chars >
+ * total_chars; with n > 0, d_seq, d_ack, d_flags, d_valid or d_pointer NULL.
+ *
+ * rudp_acknowledge: reply datagrams in, everything above and the closing
+ * datagram out, in one call.  d_frames, frames_bytes, d_frame_off[n + 1],
+ * len_hint, n, d_csum_in_or_null and layout as rudp_decode_varlen_checked
+ * takes them; then the arguments of rudp_ack_progress.  Outputs through *out:
+ *   seq, ack, flags, ok, csum_out_or_null
+ *                 as rudp_decode_varlen_checked writes them
+ *   usable        u8: 1 when ok is RUDP_OK_GOOD or RUDP_OK_UNVERIFIED.  A short
+ *                 frame, a wrong checksum and bad offsets are not usable; UTF-8
+ *                 validity is not required (wait_ack never reads the payload)
+ *   valid, pointer, state_out[4] (may be d_state_in), info[8]
+ *                 as rudp_ack_progress, with `usable` as its mask
+ *   final_frame   `layout` bytes: Packet().to_byte() of the closing datagram
+ *                 (for layout 7 with its RFC 1071 checksum in-band), written
+ *                 only when end < n
+ *   final_csum_or_null  u16[1]: its checksum, written with it
+ *   status        u32, required: 0, or RUDP_ST_OFFSETS when a frame was
+ *                 rejected for its offsets (it is not usable and none of its
+ *                 bytes is read)
+ * Every table is bit for bit what rudp_decode_varlen_checked, the usable rule
+ * and rudp_ack_progress write when called one after another.  A batch of at
+ * most 1024 replies in at most 32768 bytes and 261 bytes per reply is one
+ * launch of one workgroup that reads the frames once; larger batches run the
+ * decode, a usable pass, the rule's launches and a closing builder.  n == 0
+ * copies the state, writes info and status = 0, and touches nothing else.
+ * RUDP_EINVAL before any HIP call: out NULL; a layout other than 5 or 7; a
+ * sideband d_csum_in with layout 7; the scalar checks of rudp_ack_progress;
+ * d_state_in, state_out, info or status NULL; with n > 0, d_frame_off,
+ * final_frame or any table other than csum_out_or_null NULL, or d_frames NULL
+ * with frames_bytes > 0.
+ */
+#define RUDP_HAS_ACKNOWLEDGE 1
+#define RUDP_ACK_EXACT 0
+#define RUDP_ACK_CUMULATIVE 1
+typedef struct rudp_acknowledged {
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint8_t* ok;
+  uint16_t* csum_out_or_null;
+  uint8_t* usable;
+  uint8_t* valid;
+  uint64_t* pointer;
+  uint64_t* state_out;
+  uint64_t* info;
+  uint8_t* final_frame;
+  uint16_t* final_csum_or_null;
+  uint32_t* status;
+} rudp_acknowledged;
+RUDP_API int rudp_ack_progress(const uint16_t* d_seq, const uint16_t* d_ack, const uint8_t* d_flags,
+                               const uint8_t* d_usable_or_null, uint64_t n, uint32_t isn, uint64_t total_chars,
+                               uint32_t chunk_chars, int mode, uint64_t sent_chars, const uint64_t* d_state_in,
+                               uint8_t* d_valid, uint64_t* d_pointer, uint64_t* d_state_out, uint64_t* d_info,
+                               int device, void* hip_stream);
+RUDP_API int rudp_acknowledge(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
+                              uint32_t len_hint, uint64_t n, const uint16_t* d_csum_in_or_null, uint32_t isn,
+                              uint64_t total_chars, uint32_t chunk_chars, int mode, uint64_t sent_chars,
+                              const uint64_t* d_state_in, const rudp_acknowledged* out, int layout, int device,
+                              void* hip_stream);
+
+/*
  * Bounds of a variable-length batch, computed on the device (argument checks
  * the varlen entry points need before they can size or trust a buffer; the
  * reference has no batch and so no counterpart).  Synchronous on hip_stream.

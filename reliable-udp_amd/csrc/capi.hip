@@ -1226,6 +1226,145 @@ int rudp_receive(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t*
   return 0;
 }
 
+// The scalar arguments the two acknowledge entries share.
+static int ack_check_scalars(const char* who, uint32_t isn, uint64_t total_chars, uint32_t chunk_chars, int mode,
+                             uint64_t sent_chars) {
+  if (isn > 65535u) return fail(RUDP_EINVAL, "%s: isn %u above 65535", who, isn);
+  if (chunk_chars < 1u || chunk_chars > 16383u)
+    return fail(RUDP_EINVAL, "%s: chunk_chars %u outside [1, 16383]", who, chunk_chars);
+  if (mode != RUDP_ACK_EXACT && mode != RUDP_ACK_CUMULATIVE)
+    return fail(RUDP_EINVAL, "%s: mode %d (use RUDP_ACK_EXACT or RUDP_ACK_CUMULATIVE)", who, mode);
+  if (sent_chars > total_chars)
+    return fail(RUDP_EINVAL, "%s: sent_chars %llu exceeds total_chars %llu", who, (unsigned long long)sent_chars,
+                (unsigned long long)total_chars);
+  return 0;
+}
+
+int rudp_ack_progress(const uint16_t* d_seq, const uint16_t* d_ack, const uint8_t* d_flags,
+                      const uint8_t* d_usable_or_null, uint64_t n, uint32_t isn, uint64_t total_chars,
+                      uint32_t chunk_chars, int mode, uint64_t sent_chars, const uint64_t* d_state_in,
+                      uint8_t* d_valid, uint64_t* d_pointer, uint64_t* d_state_out, uint64_t* d_info, int device,
+                      void* hip_stream) {
+  if (!d_state_in) return fail(RUDP_EINVAL, "rudp_ack_progress: d_state_in is NULL");
+  if (!d_state_out) return fail(RUDP_EINVAL, "rudp_ack_progress: d_state_out is NULL");
+  if (!d_info) return fail(RUDP_EINVAL, "rudp_ack_progress: d_info is NULL");
+  int rc = ack_check_scalars("rudp_ack_progress", isn, total_chars, chunk_chars, mode, sent_chars);
+  if (rc) return rc;
+  if (n) {
+    if (!d_seq) return fail(RUDP_EINVAL, "rudp_ack_progress: d_seq is NULL");
+    if (!d_ack) return fail(RUDP_EINVAL, "rudp_ack_progress: d_ack is NULL");
+    if (!d_flags) return fail(RUDP_EINVAL, "rudp_ack_progress: d_flags is NULL");
+    if (!d_valid) return fail(RUDP_EINVAL, "rudp_ack_progress: d_valid is NULL");
+    if (!d_pointer) return fail(RUDP_EINVAL, "rudp_ack_progress: d_pointer is NULL");
+  }
+  DeviceScope dev_scope;
+  rc = dev_scope.set(device);
+  if (rc) return rc;
+  AckArgs a{};
+  a.ack = d_ack;
+  a.flags = d_flags;
+  a.usable = d_usable_or_null;
+  a.n = n;
+  a.isn = isn;
+  a.mode = (uint32_t)mode;
+  a.T = total_chars;
+  a.C = chunk_chars;
+  a.sent = sent_chars;
+  a.state_in = d_state_in;
+  a.state_out = d_state_out;
+  a.valid = d_valid;
+  a.pointer = d_pointer;
+  a.info = d_info;
+  ScratchCall call((hipStream_t)hip_stream);  // the tile maxima, until the last launch
+  rc = launch_ack_progress(a, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "acknowledgement progress launch");
+  return 0;
+}
+
+int rudp_acknowledge(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off, uint32_t len_hint,
+                     uint64_t n, const uint16_t* d_csum_in_or_null, uint32_t isn, uint64_t total_chars,
+                     uint32_t chunk_chars, int mode, uint64_t sent_chars, const uint64_t* d_state_in,
+                     const rudp_acknowledged* out, int layout, int device, void* hip_stream) {
+  if (!out) return fail(RUDP_EINVAL, "rudp_acknowledge: out is NULL");
+  if (layout != RUDP_LAYOUT_RUDP5 && layout != RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "unsupported layout %d (use 5 or 7)", layout);
+  if (d_csum_in_or_null && layout == RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "rudp_acknowledge: d_csum_in with layout 7 (its checksum is in-band)");
+  int rc = ack_check_scalars("rudp_acknowledge", isn, total_chars, chunk_chars, mode, sent_chars);
+  if (rc) return rc;
+  if (!d_state_in) return fail(RUDP_EINVAL, "rudp_acknowledge: d_state_in is NULL");
+  if (!out->state_out) return fail(RUDP_EINVAL, "rudp_acknowledge: state_out is NULL");
+  if (!out->info) return fail(RUDP_EINVAL, "rudp_acknowledge: info is NULL");
+  if (!out->status) return fail(RUDP_EINVAL, "rudp_acknowledge: status is NULL");
+  if (n) {
+    if (!d_frame_off) return fail(RUDP_EINVAL, "rudp_acknowledge: d_frame_off is NULL");
+    if (!d_frames && frames_bytes) return fail(RUDP_EINVAL, "rudp_acknowledge: d_frames is NULL");
+    const struct {
+      const void* p;
+      const char* name;
+    } tables[] = {{out->seq, "seq"},       {out->ack, "ack"},     {out->flags, "flags"},     {out->ok, "ok"},
+                  {out->usable, "usable"}, {out->valid, "valid"}, {out->pointer, "pointer"},
+                  {out->final_frame, "final_frame"}};
+    for (const auto& t : tables)
+      if (!t.p) return fail(RUDP_EINVAL, "rudp_acknowledge: %s is NULL", t.name);
+  }
+  DeviceScope dev_scope;
+  rc = dev_scope.set(device);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  AcknowledgeArgs a{};
+  a.r.ack = out->ack;
+  a.r.flags = out->flags;
+  a.r.usable = out->usable;
+  a.r.n = n;
+  a.r.isn = isn;
+  a.r.mode = (uint32_t)mode;
+  a.r.T = total_chars;
+  a.r.C = chunk_chars;
+  a.r.sent = sent_chars;
+  a.r.state_in = d_state_in;
+  a.r.state_out = out->state_out;
+  a.r.valid = out->valid;
+  a.r.pointer = out->pointer;
+  a.r.info = out->info;
+  // the frames pointer moved back to a 16-B boundary: every load is an aligned block
+  a.fmis = reinterpret_cast<uintptr_t>(d_frames) & 15u;
+  a.frames = d_frames - a.fmis;
+  a.frames_bytes = frames_bytes;
+  a.frame_off = d_frame_off;
+  a.csum_in = d_csum_in_or_null;
+  a.H = (uint32_t)layout;
+  a.seq = out->seq;
+  a.ack = out->ack;
+  a.flags = out->flags;
+  a.ok = out->ok;
+  a.csum_out = out->csum_out_or_null;
+  a.usable = out->usable;
+  a.final_frame = out->final_frame;
+  a.final_csum = out->final_csum_or_null;
+  a.status = out->status;
+  if (acknowledge_fused_ok(n, frames_bytes)) {
+    rc = launch_acknowledge_fused(a, s);
+    if (rc) return hip_fail((hipError_t)rc, "fused acknowledge launch");
+    return 0;
+  }
+  // The chained form: the decode's launches, usable[], the rule's launches and
+  // the closing builder back to back on the stream, their temporaries from one
+  // set.  The decode writes the call's status.
+  ScratchCall call(s);
+  rc = rudp_decode_varlen_checked(d_frames, frames_bytes, d_frame_off, len_hint, n, d_csum_in_or_null, a.seq, a.ack,
+                                  a.flags, a.ok, a.csum_out, a.status, layout, device, hip_stream);
+  if (rc) return rc;
+  rc = launch_ack_usable(a.ok, a.usable, n, s);
+  if (rc) return hip_fail((hipError_t)rc, "usable mask launch");
+  rc = rudp_ack_progress(a.seq, a.ack, a.flags, a.usable, n, isn, total_chars, chunk_chars, mode, sent_chars,
+                         d_state_in, a.r.valid, a.r.pointer, a.r.state_out, a.r.info, device, hip_stream);
+  if (rc) return rc;
+  rc = launch_ack_final_frame(a, s);
+  if (rc) return hip_fail((hipError_t)rc, "closing datagram launch");
+  return 0;
+}
+
 int rudp_varlen_bounds(const uint32_t* d_len, const int64_t* d_payload_off_or_null, uint64_t n,
                        int64_t* h_out, int device, void* hip_stream) {
   if (!h_out) return fail(RUDP_EINVAL, "rudp_varlen_bounds: h_out is NULL");

@@ -320,6 +320,47 @@ struct ReceiveArgs {
   uint64_t* tiles;              // chained form: the reply builder's tile pairs (set by the launcher)
 };
 
+// The sender's judgement of a reply batch (acknowledge.hip).
+struct AckArgs {
+  const uint16_t* ack;
+  const uint8_t* flags;
+  const uint8_t* usable;        // [n], or null: every reply usable
+  uint64_t n;
+  uint32_t isn;                 // at most 65535
+  uint32_t mode;                // RUDP_ACK_EXACT or RUDP_ACK_CUMULATIVE
+  uint64_t T;                   // total_chars
+  uint64_t C;                   // chunk_chars (1..16383)
+  uint64_t sent;                // sent_chars (CUMULATIVE mode)
+  const uint64_t* state_in;     // {p, L, last, done}
+  uint64_t* state_out;          // may be state_in
+  uint8_t* valid;
+  uint64_t* pointer;
+  uint64_t* info;               // [8]
+  uint64_t* hdr;                // more than one tile: the call's scratch (set by the launcher)
+};
+
+// Reply datagrams to sender state and closing datagram (acknowledge.hip): the
+// decode's arguments, the rule's (r reads the tables the decode writes) and
+// the closing frame.
+struct AcknowledgeArgs {
+  AckArgs r;
+  const unsigned char* frames;  // moved back to a 16-B boundary by the C entry point
+  uint64_t fmis;                // distance of the caller's frames[0] from it (0..15)
+  uint64_t frames_bytes;        // size of the caller's buffer: the offset rule's limit
+  const uint64_t* frame_off;    // [n + 1]
+  const uint16_t* csum_in;      // rudp5 sideband, may be null
+  uint32_t H;
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint8_t* ok;
+  uint16_t* csum_out;           // may be null
+  uint8_t* usable;
+  unsigned char* final_frame;   // [H], written when end < n
+  uint16_t* final_csum;         // [1], may be null
+  uint32_t* status;
+};
+
 constexpr uint32_t kTileMaxPayload = 4096;
 // Largest payload accepted: a UDP datagram's size field is 16 bits, and it
 // keeps every per-packet word sum exact in 32 bits (32768 words x 0xFFFF).
@@ -522,6 +563,10 @@ struct Tuning {
   // the one-workgroup fused kernel (1; 2: also past its mean frame length, for
   // sweeps) or the chain of the existing launches (0).
   RUDP_KNOB(receive_fused, 1)
+  // rudp_acknowledge of a batch of at most 1024 replies and kAckFusedBytes bytes:
+  // the one-workgroup fused kernel (1; 2: also past its mean frame length, for
+  // sweeps) or the chain of the decode, usable, rule and closing launches (0).
+  RUDP_KNOB(acknowledge_fused, 1)
   RUDP_KNOB(host_slots, 3)     // *_host pipeline: device staging slots (2..8)
   RUDP_KNOB(host_stage_mb, 128)  // *_host pipeline: MiB per slot (1M x 1472 B pinned: 33 ms at 128 vs 94 ms at 32)
   RUDP_KNOB(host_min_chunks, 4)  // *_host pipeline: batches over 4 MiB go as at least this many chunks (copy overlap)
@@ -660,6 +705,17 @@ bool receive_fused_ok(uint64_t n, uint64_t frames_bytes);
 int launch_receive_fused(const ReceiveArgs& args, hipStream_t stream);
 int launch_receive_usable(const uint8_t* ok, const uint8_t* valid, uint8_t* usable, uint64_t n, hipStream_t stream);
 int launch_receive_replies(ReceiveArgs args, hipStream_t stream);
+// rudp_ack_progress (acknowledge.hip): one launch for a batch of at most 1024
+// replies, else five with the tile maxima in the stream's scratch (inside a
+// ScratchCall).  rudp_acknowledge: the fused form (one workgroup from frames to
+// state and closing datagram; acknowledge_fused_ok says whether a batch takes
+// it, n == 0 always does), and the chained form's own two steps: usable[] from
+// ok[], and the closing datagram from what the rule left in info and state_out.
+int launch_ack_progress(AckArgs args, hipStream_t stream);
+bool acknowledge_fused_ok(uint64_t n, uint64_t frames_bytes);
+int launch_acknowledge_fused(const AcknowledgeArgs& args, hipStream_t stream);
+int launch_ack_usable(const uint8_t* ok, uint8_t* usable, uint64_t n, hipStream_t stream);
+int launch_ack_final_frame(const AcknowledgeArgs& args, hipStream_t stream);
 // Span starts for the byte-tiled varlen encode: rec[k] (k = 0 .. count) holds
 // p, the first packet whose packed payload starts at or after k * bytes, and
 // fo = frame_off[p], so a tile has its packet range and frame run from two

@@ -288,6 +288,8 @@ RUDP_API int rudpx_copy_vpt(const void* src, void* dst, uint64_t n16, int vpt, i
 // 79: in-order acceptance of at most 1024 frames in one launch (1) or five (0).
 // 80: rudp_receive of at most 1024 frames and kRecvFusedBytes in the fused kernel (1; 2: also past
 //     its mean frame length) or chained (0).
+// 81: rudp_acknowledge of at most 1024 replies and kAckFusedBytes in the fused kernel (1; 2: also past
+//     its mean frame length) or chained (0).
 // (72: a first-round stagger of half the fused decode tiles' workgroups (s_sleep),
 // 0.539 -> 0.540-0.543 ms on multi-byte text, ASCII 0.229 -> 0.231-0.233: removed;
 // profiles/r05/sweeps/utf8_decode_stagger.json.)
@@ -352,7 +354,8 @@ RUDP_API int rudpx_tune(int key, int value) {
             : key == 77 ? &t.segment_apron
             : key == 78 ? &t.chars_glog
             : key == 79 ? &t.accept_single
-            : key == 80 ? &t.receive_fused : nullptr;
+            : key == 80 ? &t.receive_fused
+            : key == 81 ? &t.acknowledge_fused : nullptr;
   if (!slot) return -22;
   return slot->exchange(value);
 }

@@ -43,8 +43,9 @@ EXPORTS = (
     "rudp_dedup_stream_create", "rudp_dedup_stream_push", "rudp_dedup_stream_counts", "rudp_dedup_stream_destroy",
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
     "rudp_gather_payloads", "rudp_segment_utf8", "rudp_payload_chars", "rudp_accept_inorder",
-    "rudp_receive",
+    "rudp_receive", "rudp_ack_progress", "rudp_acknowledge",
 )
+ACK_EXACT, ACK_CUMULATIVE = 0, 1  # RUDP_ACK_*: the mode of rudp_ack_progress / rudp_acknowledge
 
 
 class RudpBatch(ctypes.Structure):
@@ -69,6 +70,13 @@ class RudpReceived(ctypes.Structure):
         "reply_ack", "state_out", "payload")] + [("payload_cap", ctypes.c_uint64)] + [
         (name, ctypes.c_void_p) for name in (
             "payload_off", "reply_frames", "reply_csum", "reply_index", "reply_peer", "info", "status")]
+
+
+class RudpAcknowledged(ctypes.Structure):
+    """struct rudp_acknowledged (include/rudp.h): the output pointers of rudp_acknowledge."""
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "seq", "ack", "flags", "ok", "csum_out", "usable", "valid", "pointer", "state_out", "info", "final_frame",
+        "final_csum", "status")]
 
 
 class RudpError(RuntimeError):
@@ -113,6 +121,9 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rudp_payload_chars": [P, U64, P, U32, U64, P, I, I, P],
         "rudp_accept_inorder": [P, P, P, P, U64, U32, P, P, P, P, P, P, P, I, P],
         "rudp_receive": [P, U64, P, U32, U64, P, U32, P, ctypes.POINTER(RudpReceived), I, I, P],
+        "rudp_ack_progress": [P, P, P, P, U64, U32, U64, U32, I, U64, P, P, P, P, P, I, P],
+        "rudp_acknowledge": [P, U64, P, U32, U64, P, U32, U64, U32, I, U64, P, ctypes.POINTER(RudpAcknowledged), I, I,
+                             P],
         "rudp_dedup_stream_create": [U32, U32, U32, I, P, ctypes.POINTER(ctypes.c_void_p)],
         "rudp_dedup_stream_push": [P, P, P, U64, P, P],
         "rudp_dedup_stream_counts": [P, P],

@@ -1422,6 +1422,304 @@ def receive(frames, frame_off, layout: Union[str, int] = "rudp7", *, csum=None, 
     return Received(buf, n, H, cap)
 
 
+# ------------------------------------------------------------ replies -> sender state
+# The geometry of csrc/acknowledge.hip (tests/test_ack_api.py holds these to the source).
+ACK_TILE = 1024            # replies per tile of rudp_ack_progress; a batch up to one tile is one launch
+ACK_FUSED_BYTES = 32768    # rudp_acknowledge: a batch of at most ACK_TILE replies in at most this many bytes ...
+ACK_FUSED_MEAN = 261       # ... and this many per reply is one launch of one workgroup
+ACK_MODES = {"exact": _native.ACK_EXACT, "cumulative": _native.ACK_CUMULATIVE}
+
+
+def fresh_ack_state(total_chars: int, chunk: int = 1):
+    """(p, L, last, done) at the start of a ``send()``: nothing acknowledged, the
+    first frame outstanding."""
+    first = min(chunk, total_chars)
+    return 0, first, int(first == total_chars), 0
+
+
+class _AckResult:
+    """What ``AckProgress`` and ``Acknowledged`` share: views of the one
+    allocation by name, and the host reads of ``info`` (one synchronization on
+    first use, cached)."""
+
+    __slots__ = ("_buf", "_n", "_lay", "_views", "_info")
+
+    def _cut(self, name, nbytes, dtype):
+        v = self._views.get(name)
+        if v is None:
+            lo = self._lay[name]
+            v = self._buf[lo:lo + nbytes]
+            v = self._views[name] = v if dtype is None else v.view(dtype)
+        return v
+
+    valid = property(lambda self: self._cut("valid", self._n, None))
+
+    @property
+    def pointer(self):
+        import torch
+        return self._cut("pointer", 8 * self._n, torch.int64)
+
+    @property
+    def state(self):
+        """int64 [4] on the device: p, L, last, done after the call; pass it as
+        ``state=`` of the next call."""
+        import torch
+        return self._cut("state", 32, torch.int64)
+
+    @property
+    def info(self):
+        """int64 [8] on the device: end, valid replies, newly acknowledged
+        characters, p after, first_anomaly, next frame, done, 0."""
+        import torch
+        return self._cut("info", 64, torch.int64)
+
+    def _host_info(self):
+        if self._info is None:
+            self._info = [int(v) for v in self.info.tolist()]
+        return self._info
+
+    end = property(lambda self: self._host_info()[0])
+    count = property(lambda self: self._host_info()[1])
+    newly_acknowledged = property(lambda self: self._host_info()[2])
+    pointer_after = property(lambda self: self._host_info()[3])
+    first_anomaly = property(lambda self: self._host_info()[4])
+    next_frame = property(lambda self: self._host_info()[5])
+    done = property(lambda self: bool(self._host_info()[6]))
+    fast = property(lambda self: self._host_info()[4] == self._n)
+
+    def __len__(self) -> int:
+        return self._n
+
+
+class AckProgress(_AckResult):
+    """Result of ``ack_progress``: ``valid`` (u8 [N]) and ``pointer`` (int64
+    [N], the characters acknowledged after each reply) as rudp_ack_progress
+    defines them, ``state`` (int64 [4] on the device, for the next call's
+    ``state=``) and ``info``.  ``end`` (N when no valid reply had FIN),
+    ``count`` (valid replies), ``newly_acknowledged``, ``pointer_after``,
+    ``first_anomaly``, ``fast`` (the one-scan form was exact), ``next_frame``
+    (the row of ``segment_message``'s table to send next) and ``done`` are read
+    from the device on first use, one synchronization for all; nothing else
+    waits."""
+
+    __slots__ = ()
+
+    def __init__(self, buf, n: int):
+        self._buf, self._n, self._lay = buf, n, AckProgress.layout(n)
+        self._views, self._info = {}, None
+
+    @staticmethod
+    def layout(n: int):
+        """Byte offsets in the one allocation: pointer (u64 [n]) | state (u64
+        [4]) | info (u64 [8]) | valid (u8 [n]); ``size`` is the allocation's."""
+        return {"pointer": 0, "state": 8 * n, "info": 8 * n + 32, "valid": 8 * n + 96, "size": 9 * n + 96}
+
+
+def _ack_scalars(isn, total_chars, chunk, mode, sent):
+    for name, v in (("isn", isn), ("total_chars", total_chars), ("chunk", chunk)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be a non-negative int, got {v!r}")
+    if isn > 0xFFFF:
+        raise ValueError(f"isn must be at most 65535, got {isn}")
+    chunk = _check_chunk(chunk)
+    try:
+        m = ACK_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"mode must be 'exact' or 'cumulative', got {mode!r}") from None
+    if sent is None:
+        sent = total_chars
+    if isinstance(sent, bool) or not isinstance(sent, int) or not 0 <= sent <= total_chars:
+        raise ValueError(f"sent must lie in [0, total_chars], got {sent!r}")
+    return chunk, m, sent
+
+
+_FRESH_ACK = {}  # (device index, L, last) -> the fresh state on the device; only ever read
+
+
+def _ack_state(state, dev, total_chars, chunk):
+    import torch
+    if _is_torch(state):
+        _int_tensor(state, "state", dev, 4, dtypes=(torch.int64,))
+        return state
+    if state is None:
+        # One tensor per device and first frame, made outside any stream capture and
+        # complete before it is first used (the one wait), as _accept_state keeps its
+        # zero state: later calls on any stream, captured ones included, may read it.
+        fresh = fresh_ack_state(total_chars, chunk)
+        key = (dev.index if dev.index is not None else torch.cuda.current_device(),) + fresh[1:3]
+        t = _FRESH_ACK.get(key)
+        if t is None:
+            t = torch.tensor(fresh, dtype=torch.int64).to(dev)
+            if torch.cuda.is_current_stream_capturing():
+                return t
+            torch.cuda.current_stream(dev).synchronize()
+            if len(_FRESH_ACK) < 64:
+                _FRESH_ACK[key] = t
+        return t
+    try:
+        p, L, last, done = (int(v) for v in state)
+    except (TypeError, ValueError):
+        raise TypeError("state must be None, (p, L, last, done) or the state tensor of a previous result") from None
+    if p < 0 or L < 0:
+        raise ValueError("state: p and L must not be negative")
+    return torch.tensor([p, L, 1 if last else 0, 1 if done else 0], dtype=torch.int64).to(dev)
+
+
+def ack_progress(seq, ack, flags, *, isn: int, total_chars: int, chunk: int = 1, usable=None, state=None,
+                 mode: str = "exact", sent: Optional[int] = None, stream=None) -> AckProgress:
+    """What the reference's sender makes of a batch of replies, in arrival order
+    (``wait_ack``, utils/reliableUDP.py:64-85: a reply counts when its ack_num
+    is ISN + characters acknowledged + characters outstanding), on the device
+    with no host wait (rudp_ack_progress; include/rudp.h states the rule).
+
+    ``seq``, ``ack`` (u16 [N]) and ``flags`` (u8 [N]) as the decode returns
+    them, ``usable`` a u8 or bool [N] tensor (None: every reply).  ``isn``,
+    ``total_chars`` and ``chunk`` are the constants of the ``send()``.
+    ``state``: None (a fresh transfer), ``(p, L, last, done)``, or the
+    ``state`` of the previous call's result.  (The first ``state=None`` call
+    for a first frame's size on a device waits once for its fresh state to be
+    written; no later call waits.)  ``mode="cumulative"`` takes any
+    reply on the chunk grid between the expected one and ISN + ``sent``
+    (default: ``total_chars``), for a sender with several frames in flight."""
+    if not _is_torch(seq) or not _is_torch(ack) or not _is_torch(flags):
+        raise TypeError("ack_progress takes torch tensors on a HIP device (no host-memory form)")
+    chunk, m, sent = _ack_scalars(isn, total_chars, chunk, mode, sent)
+    import torch
+    dev = seq.device
+    if dev.type != "cuda":
+        raise ValueError("ack_progress runs on a HIP device")
+    _dev_check(seq, "seq", torch.uint16, 1, dev)
+    n = seq.shape[0]
+    _int_tensor(ack, "ack", dev, n, dtypes=(torch.uint16,))
+    _int_tensor(flags, "flags", dev, n, dtypes=(torch.uint8,))
+    if usable is not None:
+        _int_tensor(usable, "usable", dev, n, dtypes=(torch.uint8, torch.bool))
+    st = _ack_state(state, dev, total_chars, chunk)
+    lay = AckProgress.layout(n)
+    buf = torch.empty(lay["size"], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+    tab = n > 0
+    _native.check(_native.lib().rudp_ack_progress(
+        seq.data_ptr() if tab else None, ack.data_ptr() if tab else None, flags.data_ptr() if tab else None,
+        usable.data_ptr() if usable is not None and tab else None, n, isn, total_chars, chunk, m, sent,
+        st.data_ptr(), base + lay["valid"] if tab else None, base + lay["pointer"] if tab else None,
+        base + lay["state"], base + lay["info"], dev.index or 0, _stream_ptr(stream, dev)))
+    return AckProgress(buf, n)
+
+
+class Acknowledged(_AckResult):
+    """Result of ``acknowledge``: one allocation, every member a view of it.
+
+    ``seq``, ``ack``, ``csum`` (u16 [N]), ``flags``, ``ok`` (u8 [N]) as
+    ``unpack_batch_varlen`` returns them; ``usable`` (u8 [N]: the checksum and
+    the frame's shape are good; UTF-8 is not looked at); ``valid``,
+    ``pointer``, ``state``, ``info`` and the host reads as ``AckProgress``;
+    ``final_frame`` (u8 [H]: the closing ``send_ack`` datagram, written when
+    ``done`` became true in this batch, ``end < N``), ``final_csum`` (u16 [1])
+    and ``status`` (int32 [1], RUDP_ST_* of the call) on the device."""
+
+    __slots__ = ("_H",)
+
+    def __init__(self, buf, n: int, H: int):
+        self._buf, self._n, self._H, self._lay = buf, n, H, Acknowledged.layout(n, H)
+        self._views, self._info = {}, None
+
+    @staticmethod
+    def layout(n: int, H: int):
+        """Byte offsets in the one allocation, every array aligned to its
+        element; ``size`` is the allocation's."""
+        lay, at = {}, 0
+        for name, nbytes in (("pointer", 8 * n), ("state", 32), ("info", 64), ("status", 8),
+                             ("seq", 2 * n), ("ack", 2 * n), ("csum", 2 * n), ("final_csum", 2),
+                             ("flags", n), ("ok", n), ("usable", n), ("valid", n), ("final_frame", 8)):
+            lay[name] = at
+            at += nbytes
+        lay["size"] = at
+        return lay
+
+    def _u16(self, name):
+        import torch
+        return self._cut(name, 2 * self._n, torch.uint16)
+
+    seq = property(lambda self: self._u16("seq"))
+    ack = property(lambda self: self._u16("ack"))
+    csum = property(lambda self: self._u16("csum"))
+    flags = property(lambda self: self._cut("flags", self._n, None))
+    ok = property(lambda self: self._cut("ok", self._n, None))
+    usable = property(lambda self: self._cut("usable", self._n, None))
+    final_frame = property(lambda self: self._cut("final_frame", self._H, None))
+
+    @property
+    def final_csum(self):
+        import torch
+        return self._cut("final_csum", 2, torch.uint16)
+
+    @property
+    def status(self):
+        import torch
+        return self._cut("status", 4, torch.int32)
+
+    def check(self) -> "Acknowledged":
+        """Raise ValueError if the device rejected a frame's offsets; one synchronization."""
+        _raise_status(self.status)
+        return self
+
+
+def acknowledge(frames, frame_off, layout: Union[str, int] = "rudp7", *, isn: int, total_chars: int, chunk: int = 1,
+                state=None, mode: str = "exact", sent: Optional[int] = None, csum=None, stream=None) -> Acknowledged:
+    """A batch of reply datagrams (packed frames, as recvmmsg leaves them) turned
+    into the sender's new state and, when the receiver's FIN is among them, the
+    closing ``send_ack`` datagram of utils/reliableUDP.py:87-93, in one library
+    call with no host wait (rudp_acknowledge).  A batch of at most ``ACK_TILE``
+    replies in at most ``ACK_FUSED_BYTES`` bytes (and ``ACK_FUSED_MEAN`` per
+    reply) is one kernel launch.
+
+    ``frames`` (u8 1-D), ``frame_off`` (int64 [N + 1]) and ``csum`` (u16 [N],
+    the rudp5 sideband; None: rudp5 frames are taken unverified) are device
+    tensors; the rest as ``ack_progress`` takes them.  Every array equals what
+    ``unpack_batch_varlen``, the usable rule and ``ack_progress`` return for the
+    same input."""
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off):
+        raise TypeError("acknowledge takes torch tensors on a HIP device (no host-memory form)")
+    chunk, m, sent = _ack_scalars(isn, total_chars, chunk, mode, sent)
+    import torch
+    dev = frames.device
+    if dev.type != "cuda":
+        raise ValueError("acknowledge runs on a HIP device")
+    _dev_check(frames, "frames", torch.uint8, 1, dev)
+    _int_tensor(frame_off, "frame_off", dev, dtypes=(torch.int64,))
+    n = frame_off.shape[0] - 1
+    if n < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    if csum is not None:
+        if H == 7:
+            raise ValueError("rudp7 carries its checksum in-band; csum is for rudp5")
+        _dev_check(csum, "csum", torch.uint16, 1, dev)
+        if csum.shape[0] != n:
+            raise ValueError(f"csum has {csum.shape[0]} entries for {n} frames")
+    st = _ack_state(state, dev, total_chars, chunk)
+    nbytes = frames.numel()
+    lay = Acknowledged.layout(n, H)
+    buf = torch.empty(lay["size"], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+
+    def tab(name):
+        return base + lay[name] if n else None
+
+    out = _native.RudpAcknowledged(
+        seq=tab("seq"), ack=tab("ack"), flags=tab("flags"), ok=tab("ok"), csum_out=tab("csum"),
+        usable=tab("usable"), valid=tab("valid"), pointer=tab("pointer"), state_out=base + lay["state"],
+        info=base + lay["info"], final_frame=base + lay["final_frame"], final_csum=base + lay["final_csum"],
+        status=base + lay["status"])
+    _native.check(_native.lib().rudp_acknowledge(
+        frames.data_ptr() if nbytes else None, nbytes, frame_off.data_ptr(),
+        min(nbytes // n, 0xFFFFFFFF) if n else 0, n, csum.data_ptr() if csum is not None and n else None,
+        isn, total_chars, chunk, m, sent, st.data_ptr(), ctypes.byref(out), H, dev.index or 0,
+        _stream_ptr(stream, dev)))
+    return Acknowledged(buf, n, H)
+
+
 # ------------------------------------------------------------ message -> datagrams
 MAX_CHUNK = 16383  # characters per datagram: 4 * 16383 <= 65535 payload bytes
 

@@ -260,3 +260,37 @@ class BatchReceiver:
         for t in (d_frames, d_off, res._buf):  # the result's members are views of one buffer
             t.record_stream(cur)
         return res, d_frames, d_off
+
+    def acknowledge(self, layout="rudp5", *, isn, total_chars, chunk=1, state=None, mode="exact", sent=None,
+                    csum=None, stream=None):
+        """H2D of the received reply datagrams as ``receive()`` does it (the same
+        slot and event bookkeeping), then ``batch.acknowledge``: the sender's
+        judgement of the batch, its new state and, at the receiver's FIN, the
+        closing datagram, in one library call.  Never waits for the device.  The
+        arguments as ``batch.acknowledge`` takes them (the previous result's
+        ``state`` carries a transfer from batch to batch).
+
+        Returns ``(Acknowledged, d_frames, d_frame_off)``."""
+        import torch
+        s = stream if stream is not None else self.stream
+        k, n = self._slot, self.count
+        if k < 0:
+            raise RuntimeError("acknowledge() before any recv()")
+        total = int(self._off_t[k][n])
+        s.wait_stream(torch.cuda.current_stream(self.device))  # e.g. csum or state written by the caller
+        with torch.cuda.stream(s):
+            d_frames = torch.empty((total,), dtype=torch.uint8, device=self.device)
+            d_off = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+            d_frames.copy_(self._frames_t[k][:total], non_blocking=True)
+            d_off.copy_(self._off_t[k][:n + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(s)
+            self._copied[k] = ev
+            res = _batch.acknowledge(d_frames, d_off, layout, isn=isn, total_chars=total_chars, chunk=chunk,
+                                     state=state, mode=mode, sent=sent, csum=csum, stream=s)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(s)
+        # allocated on `s`, used on the caller's stream from here on
+        for t in (d_frames, d_off, res._buf):  # the result's members are views of one buffer
+            t.record_stream(cur)
+        return res, d_frames, d_off

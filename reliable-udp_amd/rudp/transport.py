@@ -30,6 +30,15 @@ Protocol (one character of payload per datagram, utils/reliableUDP.py:11):
 GPU: every frame a transfer can send is known once the ISN is drawn, so one
 pack_batch_varlen launch (rudp5, the reference's 5-byte layout) builds the
 table and each send, retransmissions included, takes row k.  Same wire bytes.
+
+``ReliableUDP(codec_device=..., batch_send=True, window=W)`` is a windowed
+sender over the same table: up to W frames in flight (sendmmsg), the replies
+taken in recvmmsg batches and each batch judged on the GPU in one call
+(batch.acknowledge: wait_ack's rule for every reply, the new state, and the
+closing datagram at the receiver's FIN).  With W = 1 the wire carries the same
+bytes as the loop above.  ``cumulative=True`` lets a reply past the expected
+one count, so a lost reply does not cost a timeout (the reference, with one
+frame in flight, has no counterpart).
 """
 from __future__ import annotations
 
@@ -81,13 +90,23 @@ class ReliableUDP:
     PAYLOAD_SIZE = CHUNK
 
     def __init__(self, timeout=1, isn_source: Optional[Callable[[], int]] = None,
-                 codec_device: Optional[str] = None, batch_recv: bool = False):
+                 codec_device: Optional[str] = None, batch_recv: bool = False, batch_send: bool = False,
+                 window: int = 1, cumulative: bool = False):
         self.socket: socket
         self.retransmission_timeout = timeout
         self._draw_isn = isn_source or (lambda: random.randint(1, 5000))
         self._codec_device = codec_device
         if batch_recv and not codec_device:
             raise ValueError("batch_recv=True judges the datagrams on the GPU: it needs codec_device")
+        if batch_send and not codec_device:
+            raise ValueError("batch_send=True judges the replies on the GPU: it needs codec_device")
+        if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= 1024:
+            raise ValueError(f"window must be an int in [1, 1024] frames in flight, got {window!r}")
+        if (window != 1 or cumulative) and not batch_send:
+            raise ValueError("window and cumulative belong to the windowed sender: they need batch_send=True")
+        # send() keeps `window` frames in flight and judges the replies of each recvmmsg batch on the
+        # device (_transmit_window); cumulative: a reply past the expected one counts (a lost reply does not stall)
+        self._batch_send, self._window, self._cumulative = batch_send, window, cumulative
         self._batch_recv = batch_recv  # recv() over recvmmsg batches judged on the device (_recv_batches)
         self._rx: Any = None           # its BatchReceiver, made on first use
         self._last_isn: Optional[int] = None  # the previous transfer's ISN (a repeated SYN is ignored)
@@ -131,7 +150,10 @@ class ReliableUDP:
     def send(self, message: str, ip, port) -> None:
         self.flush_recv_buffer()
         try:
-            self._transmit(message, (str(ipaddress.ip_address(ip)), port))
+            if self._batch_send:
+                self._transmit_window(message, (str(ipaddress.ip_address(ip)), port))
+            else:
+                self._transmit(message, (str(ipaddress.ip_address(ip)), port))
         finally:
             self.flush_recv_buffer()
 
@@ -174,6 +196,67 @@ class ReliableUDP:
             else:
                 expect, sends_left = None, MAX_SENDS
 
+    def _batch_receiver(self):
+        """The socket's BatchReceiver (recvmmsg into pinned slots, H2D, one library call), made on first use."""
+        import torch
+        from . import netio
+        if self._rx is None or self._rx.sock is not self.socket:
+            self._rx = netio.BatchReceiver(self.socket, max_msgs=1024, slot_bytes=MAX_DATAGRAM, slots=2,
+                                           device=torch.device(self._codec_device), with_sources=True)
+        return self._rx
+
+    def _transmit_window(self, message: str, dest) -> None:
+        """_transmit with up to ``window`` frames in flight: the frames of
+        _gpu_frames go out with sendmmsg, the replies come in recvmmsg batches,
+        and each batch is judged on the device in one call (batch.acknowledge:
+        wait_ack's rule for every reply, the new state, and the closing datagram
+        at the receiver's FIN).  A timeout goes back to the frame at the
+        acknowledged pointer, as send_data does, and MAX_SENDS timeouts without
+        progress give up."""
+        import numpy as np
+        from . import netio
+        isn = self._draw_isn()
+        frames, off = self._gpu_frames(message, isn)
+        frames, off = np.frombuffer(frames, np.uint8), np.asarray(off, np.int64)
+        T, W = len(message), self._window
+        rows = max(-(-T // CHUNK), 1)  # data rows; row `rows` (T > 0) is the header-only FIN frame of a late resend
+        mode = "cumulative" if self._cumulative else "exact"
+        rx = self._batch_receiver()
+        self.socket.setblocking(True)
+
+        def put(lo, hi):
+            netio.send_batch(self.socket, frames[off[lo]:off[hi]], off[lo:hi + 1] - off[lo], *dest)
+
+        p, nxt, sends_left = 0, 0, MAX_SENDS  # characters acknowledged, next row to send, sends left for the frame at p
+        state: Any = None                      # the device's (p, L, last, done); None: a fresh transfer
+        while True:
+            base = -(-p // CHUNK)
+            hi = min(base + W, rows)
+            if nxt < hi:
+                put(nxt, hi)
+                nxt = hi
+            n = rx.recv(timeout_ms=max(int(self.retransmission_timeout * 1000), 1))
+            if n == 0:  # timeout: back to the frame at p, L and last recomputed from p (SEND_DATA)
+                L = min(CHUNK, T - p)
+                sends_left -= 1
+                if sends_left < 1:
+                    if p + L < T:
+                        print(f"\033[91mAborted after {MAX_SENDS * self.retransmission_timeout} seconds "
+                              f"({MAX_SENDS} sends of character {p} unacknowledged)\033[0m")
+                    return
+                state, nxt = (p, L, int(p + L == T), 0), base
+                if T and p == T:
+                    put(rows, rows + 1)
+                continue
+            res, _, _ = rx.acknowledge("rudp5", isn=isn, total_chars=T, chunk=CHUNK, state=state, mode=mode,
+                                       sent=min(nxt * CHUNK, T))
+            state = res.state
+            if res.done:  # (the one wait per batch; every host read below is behind it)
+                self.socket.sendto(res.final_frame.cpu().numpy().tobytes(), dest)
+                return
+            if res.pointer_after != p:
+                p, sends_left = res.pointer_after, MAX_SENDS
+
     def _gpu_frames(self, message: str, isn: int):
         """Frames for k = 0..len(message) in one GPU launch: (bytes, offsets)."""
         import numpy as np
@@ -203,12 +286,8 @@ class ReliableUDP:
         reply datagrams go out with one sendmmsg, and its part of the message
         joins the buffer.  Returns (isn, text, peer) as the loop below leaves them."""
         import numpy as np
-        import torch
         from . import netio
-        if self._rx is None or self._rx.sock is not self.socket:
-            self._rx = netio.BatchReceiver(self.socket, max_msgs=1024, slot_bytes=MAX_DATAGRAM, slots=2,
-                                           device=torch.device(self._codec_device), with_sources=True)
-        rx = self._rx
+        rx = self._batch_receiver()
         self.socket.setblocking(True)
         peer = self._peer
         state = (0, 0, 1 if peer is not None else 0)  # no transfer yet; live: there is someone to answer

@@ -433,4 +433,29 @@ uint32_t dedup_small_cap(uint32_t mean_len, uint32_t window) {
   return cap <= 16ull * kDedupVecPer * kBlock ? (uint32_t)cap : 0u;
 }
 
+#if RUDP_TOOLS
+// Diagnostics (rudpx_dedup_hashes): the hash each form computes for a frame, so
+// a test can tell that its constructed collisions still collide.
+__global__ void __launch_bounds__(kBlock) dedup_small_hash_kernel(DedupArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n) return;
+  uint64_t off;
+  uint32_t len;
+  const bool ok = frame_span(a, i, &off, &len);
+  a.hash[i] = ok ? small_hash(len, [&](uint32_t k) { return (uint32_t)a.frames[off + k]; }) : 0u;
+}
+
+int launch_dedup_hashes(const DedupArgs& args, bool small, hipStream_t stream) {
+  if (args.n == 0) return 0;
+  if (small) {
+    hipLaunchKernelGGL(dedup_small_hash_kernel, dim3((uint32_t)((args.n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       stream, args);
+  } else {
+    const uint64_t hblocks = ((args.n << args.glog) + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(dedup_hash_kernel, dim3((uint32_t)hblocks), dim3(kBlock), 0, stream, args);
+  }
+  return (int)hipGetLastError();
+}
+#endif
+
 }  // namespace rudp

@@ -7,7 +7,8 @@
 //   librudp_tools.so  RUDP_TOOLS=1, for tools/ and the tests of the non-default
 //                     kernel forms: the same ABI plus rudpx_tune (every Tuning
 //                     value a runtime knob), rudpx_encode_trace (tile timelines),
-//                     rudpx_stamp and the streaming-copy ceilings (tuning.hip).
+//                     rudpx_stamp, the streaming-copy ceilings and
+//                     rudpx_dedup_hashes (tuning.hip).
 #pragma once
 // The diagnostics build (RUDP_TOOLS) puts every internal name in a namespace
 // of its own, so its kernels and functions (whose argument structs differ
@@ -609,6 +610,12 @@ uint32_t dedup_max_window();
 // The one-launch dedup's LDS run budget for packed frames of this mean length
 // and window, or 0 when the two-pass form is used.
 uint32_t dedup_small_cap(uint32_t mean_len, uint32_t window);
+#if RUDP_TOOLS
+// Diagnostics (rudpx_dedup_hashes): args.hash[i] = the hash of frame i as the
+// two-pass forms take it (dedup_hash_kernel at args.glog), or with `small` the
+// one-launch form's 32-bit small_hash, zero-extended (0 for a rejected frame).
+int launch_dedup_hashes(const DedupArgs& args, bool small, hipStream_t stream);
+#endif
 // counts[side[i]] += (dup[i] == 1) for i < n (side null: all side 0), on `stream`.
 int launch_dedup_count(const uint8_t* dup, const uint8_t* side, uint64_t n, uint64_t* counts, hipStream_t stream);
 // Stream-ordered temporaries from a library-owned pool of the current device

@@ -390,6 +390,25 @@ RUDP_API int rudpx_scratch_stats(int device, uint64_t* out) {
   return (int)RUDP_NS::pool_used_bytes(device, &out[0]);
 }
 
+// The hash the dedup forms compute for each of n packed frames (frames
+// [frames_bytes], frame_off [n + 1], the checked offset rule): form 0..3 the
+// 64-bit hash of the two-pass forms with 2^form lanes per frame, form -1 the
+// one-launch form's 32-bit hash, zero-extended.  d_hash [n] u64.  For the
+// tests of the byte confirm, whose constructed collisions must still collide.
+RUDP_API int rudpx_dedup_hashes(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off, uint64_t n,
+                                int form, uint64_t* d_hash, void* stream) {
+  if (form < -1 || form > 3 || (n && (!d_frame_off || !d_hash))) return -22;
+  RUDP_NS::DedupArgs a{};
+  a.frames = d_frames;
+  a.frame_off = d_frame_off;
+  a.n = n;
+  a.glog = form < 0 ? 0u : (uint32_t)form;
+  a.lim_checked = 1;
+  a.frames_lim = frames_bytes;
+  a.hash = d_hash;
+  return RUDP_NS::launch_dedup_hashes(a, form < 0, (hipStream_t)stream);
+}
+
 // rudp_receive's reply builder alone (the chained form's last three launches),
 // from the tables a receive left in *out: reads seq, flags, usable, reply,
 // reply_ack and payload_off[n]; writes reply_frames, reply_csum, reply_index,

@@ -169,7 +169,7 @@ def lib() -> ctypes.CDLL:
 
 def tools_lib(activate: bool = True) -> ctypes.CDLL:
     """The diagnostics build librudp_tools.so (rudpx_tune, rudpx_encode_trace,
-    rudpx_stamp, rudpx_copy*).  ``activate``: the batch API calls it too until
+    rudpx_stamp, rudpx_copy*, rudpx_dedup_hashes).  ``activate``: the batch API calls it too until
     use_product() (its knobs only act on calls made through it)."""
     global _lib, _tools
     with _lock:
@@ -181,7 +181,8 @@ def tools_lib(activate: bool = True) -> ctypes.CDLL:
                                "rudpx_copy_tile": [P, P, U64, U32, U32, P],
                                "rudpx_copy_tile_dma": [P, P, U64, U32, U32, U32, I, P],
                                "rudpx_copy_tile_pipe": [P, P, U64, U32, U32, U32, P],
-                               "rudpx_scratch_stats": [I, P]}.items():
+                               "rudpx_scratch_stats": [I, P],
+                               "rudpx_dedup_hashes": [P, U64, P, U64, I, P, P]}.items():
                 fn = getattr(h, name)
                 fn.argtypes = args
                 fn.restype = I

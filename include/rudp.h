@@ -106,10 +106,12 @@ extern "C" {
 #define RUDP_ST_OFFSETS 8u    /* frame_off decreasing, or outside [0, frames_bytes] */
 #define RUDP_ST_PAYLOAD_CAP 16u /* gather: the kept payloads need more than payload_cap bytes */
 #define RUDP_ST_PACKETS_CAP 32u /* segment: the message makes more than max_packets packets */
+#define RUDP_ST_RANK 64u        /* gather_ordered: a rank at or above the count that is not RUDP_RANK_NONE */
 
 /* Entry points added within an ABI version, for C callers to test. */
 #define RUDP_HAS_SEGMENT_UTF8 1 /* rudp_segment_utf8 */
 #define RUDP_HAS_ACCEPT_INORDER 1 /* rudp_payload_chars, rudp_accept_inorder */
+#define RUDP_HAS_ACCEPT_WINDOW 1 /* rudp_accept_window, rudp_gather_ordered */
 
 /* Error codes (negative errno values, HIP errors offset by -1000). */
 #define RUDP_EINVAL (-22)
@@ -428,6 +430,105 @@ RUDP_API int rudp_accept_inorder(const uint16_t* d_seq, const uint8_t* d_flags, 
                                  const uint64_t* d_state_in, uint8_t* d_accept, uint8_t* d_keep,
                                  uint8_t* d_reply, uint16_t* d_reply_ack, uint64_t* d_state_out,
                                  uint64_t* d_info, int device, void* hip_stream);
+
+/*
+ * The reordering receiver of a windowed sender (added within ABI 8,
+ * RUDP_HAS_ACCEPT_WINDOW): rudp_accept_inorder's rule with a pending set, for
+ * the sender that keeps several frames in flight and takes cumulative replies
+ * (RUDP_ACK_CUMULATIVE).  Defined by this library (the reference never has
+ * two frames in flight); with window_chars == 1 nothing can be ahead inside
+ * the window and the rule is rudp_accept_inorder's.  Both calls are sync-free:
+ * asynchronous on hip_stream, the host never waits, temporaries come from the
+ * stream's set, usable under stream capture.
+ *
+ * rudp_accept_window.  d_seq, d_flags, d_chars, d_usable_or_null, n, last_isn
+ * and d_state_in = {expect, isn, live, 0} as rudp_accept_inorder takes them;
+ * window_chars (Wc) in [1, 1024]; n_carried <= min(n, 1023): the first
+ * n_carried frames are the ones the call before left pending, presented again
+ * in the order that call gave them.  They are judged as every other frame and
+ * get no reply.  The pending set is not part of the state (u64[4],
+ * interchangeable with rudp_accept_inorder's): it is empty on entry.
+ *
+ * The rule, per frame i in arrival order; P maps a start to a pending frame:
+ *   ignored    !usable_i, or syn_i && seq_i == last_isn (a reply is sent for
+ *              the latter), as rudp_accept_inorder.
+ *   reset      syn_i otherwise: isn = seq_i, expect = seq_i + c_i, live = 1;
+ *              the frames in P are rejected and P is emptied; the delivery
+ *              order restarts with this frame at rank 0 (frames delivered
+ *              before it keep accept = 1 and lose their rank); with fin_i the
+ *              transfer ends here.
+ *   in-order   a non-SYN with live && seq_i == expect (as integers): delivered,
+ *              expect += c_i; with fin_i the transfer ends here; otherwise,
+ *              while P holds a frame that starts at expect, that frame is
+ *              delivered next, its c added and the frame removed, and the
+ *              transfer ends with the first such frame that has FIN.  Then
+ *              every frame of P that starts below expect is rejected.
+ *   ahead      a non-SYN with live, expect < seq_i < expect + Wc, c_i > 0 and
+ *              no frame of P with the same start: pending (its FIN counts
+ *              when it is delivered).
+ *   else       rejected: a past frame, one at or beyond the window, c_i == 0
+ *              ahead of expect, a second frame for a pending start.
+ * A reply is sent for every usable frame i >= n_carried while live is set
+ * after it; its ack_num is expect after the frame (after the drain) mod 2^16:
+ * a cumulative acknowledgement.  `end` is the arrival index of the frame whose
+ * step delivered a FIN; P is emptied then, and the frames after `end` are not
+ * judged (every output 0, ranks RUDP_RANK_NONE).  Once expect > 65535 nothing
+ * matches.  Outputs, n entries each:
+ *   d_accept[i]     1: delivered at some point of the call; 2: pending when
+ *                   the call ends; 0 otherwise
+ *   d_rank[i]       u32: a delivered frame's position in this call's part of
+ *                   the message, in delivery order counted from the last
+ *                   reset at or before `end` (from the first delivery when
+ *                   there is none); else RUDP_RANK_NONE
+ *   d_carry_rank[i] u32: a pending frame's position among the pending ones,
+ *                   in arrival order; else RUDP_RANK_NONE
+ *   d_reply[i], d_reply_ack[i]   as rudp_accept_inorder
+ * d_state_out (u64[4], may be d_state_in); d_info (u64[8]): [0] end (n: no
+ * FIN was delivered) [1] K, the ranked frames [2] msg_start (the last reset at
+ * or before `end`, n: none) [3] characters so far [4] first_anomaly: the first
+ * frame a chunk of the device form gave to its sequential walk (n: none; see
+ * DESIGN) [5] frames pending at the end [6] frames ever delivered [7] 0.
+ * n == 0 copies the state and writes d_info = {0, 0, 0, characters, 0, 0, 0,
+ * 0}.  RUDP_EINVAL before any HIP call: d_state_in, d_state_out or d_info
+ * NULL; window_chars outside [1, 1024]; n_carried above min(n, 1023); n above
+ * 2^32 - 2; with n > 0, d_seq, d_flags, d_chars, d_accept, d_rank,
+ * d_carry_rank, d_reply or d_reply_ack NULL.
+ *
+ * rudp_gather_ordered: rudp_gather_payloads with a permutation.  Frames,
+ * frames_bytes, d_frame_off[n + 1], len_hint and n as the gather takes them;
+ * d_rank u32[n]; d_count, a device u64: the K the ranks run to, read on the
+ * device (K above n counts as n); skip in {0, 5, 7}: the bytes left out at the
+ * head of every frame.  Frame i with d_rank[i] = r < K writes max(len_i -
+ * skip, 0) bytes at d_out_off[r], the exclusive scan of those lengths in rank
+ * order: d_out_off[0..K] are written (d_out_off[K] the total) and, when not
+ * NULL, d_src_or_null[k] = the frame with rank k for k < K (RUDP_RANK_NONE
+ * when no frame has it).  With d_rank/d_info[1] and skip = layout this is the
+ * message of rudp_accept_window; with d_carry_rank/d_info[5] and skip 0, its
+ * pending frames whole, for the next call.  *d_status (required): 0, or
+ * RUDP_ST_OFFSETS when a ranked frame's offsets are decreasing or past
+ * frames_bytes (it contributes 0 bytes and is not read), RUDP_ST_RANK when a
+ * rank at or above K is not RUDP_RANK_NONE (the frame is skipped),
+ * RUDP_ST_PAYLOAD_CAP when the total exceeds out_cap (no byte of d_out is
+ * written; d_out_off[K] holds the size needed).  Nothing is written at or past
+ * the total of d_out, nor past index K of d_out_off or K - 1 of d_src.  d_out
+ * must not overlap d_frames.  The ranks below K must be distinct; when they
+ * are not the result is unspecified and every access stays in bounds.  n == 0
+ * returns 0 and touches nothing.  RUDP_EINVAL before any HIP call: skip not 0,
+ * 5 or 7; d_status or d_count NULL; n above 2^32 - 2; with n > 0, d_frame_off,
+ * d_rank or d_out_off NULL, d_frames NULL with frames_bytes > 0, d_out NULL
+ * with out_cap > 0.
+ */
+#define RUDP_RANK_NONE 0xFFFFFFFFu
+RUDP_API int rudp_accept_window(const uint16_t* d_seq, const uint8_t* d_flags, const uint32_t* d_chars,
+                                const uint8_t* d_usable_or_null, uint64_t n, uint32_t last_isn,
+                                uint32_t window_chars, uint64_t n_carried, const uint64_t* d_state_in,
+                                uint8_t* d_accept, uint32_t* d_rank, uint32_t* d_carry_rank, uint8_t* d_reply,
+                                uint16_t* d_reply_ack, uint64_t* d_state_out, uint64_t* d_info, int device,
+                                void* hip_stream);
+RUDP_API int rudp_gather_ordered(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
+                                 uint32_t len_hint, uint64_t n, const uint32_t* d_rank, const uint64_t* d_count,
+                                 uint32_t skip, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+                                 uint32_t* d_src_or_null, uint32_t* d_status, int device, void* hip_stream);
 
 /*
  * A datagram batch to message and replies in one call (added within ABI 8,

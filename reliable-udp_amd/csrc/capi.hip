@@ -1133,6 +1133,95 @@ int rudp_accept_inorder(const uint16_t* d_seq, const uint8_t* d_flags, const uin
   return 0;
 }
 
+int rudp_accept_window(const uint16_t* d_seq, const uint8_t* d_flags, const uint32_t* d_chars,
+                       const uint8_t* d_usable_or_null, uint64_t n, uint32_t last_isn, uint32_t window_chars,
+                       uint64_t n_carried, const uint64_t* d_state_in, uint8_t* d_accept, uint32_t* d_rank,
+                       uint32_t* d_carry_rank, uint8_t* d_reply, uint16_t* d_reply_ack, uint64_t* d_state_out,
+                       uint64_t* d_info, int device, void* hip_stream) {
+  if (!d_state_in) return fail(RUDP_EINVAL, "rudp_accept_window: d_state_in is NULL");
+  if (!d_state_out) return fail(RUDP_EINVAL, "rudp_accept_window: d_state_out is NULL");
+  if (!d_info) return fail(RUDP_EINVAL, "rudp_accept_window: d_info is NULL");
+  if (window_chars < 1u || window_chars > 1024u)
+    return fail(RUDP_EINVAL, "rudp_accept_window: window_chars %u outside [1, 1024]", window_chars);
+  if (n_carried > n || n_carried > 1023u)
+    return fail(RUDP_EINVAL, "rudp_accept_window: n_carried %llu above min(n, 1023)", (unsigned long long)n_carried);
+  if (n > 0xFFFFFFFEull) return fail(RUDP_EINVAL, "rudp_accept_window: n exceeds 2^32 - 2 (ranks are 32 bits)");
+  if (n) {
+    if (!d_seq) return fail(RUDP_EINVAL, "rudp_accept_window: d_seq is NULL");
+    if (!d_flags) return fail(RUDP_EINVAL, "rudp_accept_window: d_flags is NULL");
+    if (!d_chars) return fail(RUDP_EINVAL, "rudp_accept_window: d_chars is NULL");
+    if (!d_accept) return fail(RUDP_EINVAL, "rudp_accept_window: d_accept is NULL");
+    if (!d_rank) return fail(RUDP_EINVAL, "rudp_accept_window: d_rank is NULL");
+    if (!d_carry_rank) return fail(RUDP_EINVAL, "rudp_accept_window: d_carry_rank is NULL");
+    if (!d_reply) return fail(RUDP_EINVAL, "rudp_accept_window: d_reply is NULL");
+    if (!d_reply_ack) return fail(RUDP_EINVAL, "rudp_accept_window: d_reply_ack is NULL");
+  }
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  WindowArgs a{};
+  a.seq = d_seq;
+  a.flags = d_flags;
+  a.chars = d_chars;
+  a.usable = d_usable_or_null;
+  a.n = n;
+  a.n_carried = n_carried;
+  a.last_isn = last_isn;
+  a.Wc = window_chars;
+  a.state_in = d_state_in;
+  a.state_out = d_state_out;
+  a.accept = d_accept;
+  a.rank = d_rank;
+  a.carry_rank = d_carry_rank;
+  a.reply = d_reply;
+  a.reply_ack = d_reply_ack;
+  a.info = d_info;
+  ScratchCall call((hipStream_t)hip_stream);  // the state between chunks, until the last launch
+  rc = launch_accept_window(a, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "windowed acceptance launch");
+  return 0;
+}
+
+int rudp_gather_ordered(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
+                        uint32_t len_hint, uint64_t n, const uint32_t* d_rank, const uint64_t* d_count, uint32_t skip,
+                        uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_src_or_null,
+                        uint32_t* d_status, int device, void* hip_stream) {
+  (void)len_hint;  // (one tile geometry: the run of a tile is not contiguous in the frames)
+  if (skip != 0u && skip != (uint32_t)RUDP_LAYOUT_RUDP5 && skip != (uint32_t)RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "rudp_gather_ordered: skip %u (use 0, 5 or 7)", skip);
+  if (!d_status) return fail(RUDP_EINVAL, "rudp_gather_ordered: d_status is NULL");
+  if (!d_count) return fail(RUDP_EINVAL, "rudp_gather_ordered: d_count is NULL");
+  if (n > 0xFFFFFFFEull) return fail(RUDP_EINVAL, "rudp_gather_ordered: n exceeds 2^32 - 2 (ranks are 32 bits)");
+  if (n == 0) return 0;
+  if (!d_frame_off) return fail(RUDP_EINVAL, "rudp_gather_ordered: d_frame_off is NULL");
+  if (!d_rank) return fail(RUDP_EINVAL, "rudp_gather_ordered: d_rank is NULL");
+  if (!d_out_off) return fail(RUDP_EINVAL, "rudp_gather_ordered: d_out_off is NULL");
+  if (!d_frames && frames_bytes) return fail(RUDP_EINVAL, "rudp_gather_ordered: d_frames is NULL");
+  if (!d_out && out_cap) return fail(RUDP_EINVAL, "rudp_gather_ordered: d_out is NULL");
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  OrderedArgs a{};
+  // the frames pointer moved back to a 16-B boundary: every load is an aligned block
+  a.fmis = reinterpret_cast<uintptr_t>(d_frames) & 15u;
+  a.frames = d_frames - a.fmis;
+  a.frames_bytes = frames_bytes;
+  a.frame_off = d_frame_off;
+  a.rank = d_rank;
+  a.count = d_count;
+  a.n = n;
+  a.skip = skip;
+  a.out = d_out;
+  a.out_cap = out_cap;
+  a.out_off = d_out_off;
+  a.src = d_src_or_null;
+  a.status = d_status;
+  ScratchCall call((hipStream_t)hip_stream);  // the tile sums and the source table, until the last launch
+  rc = launch_gather_ordered(a, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "ordered gather launch");
+  return 0;
+}
+
 int rudp_receive(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off, uint32_t len_hint,
                  uint64_t n, const uint16_t* d_csum_in_or_null, uint32_t last_isn, const uint64_t* d_state_in,
                  const rudp_received* out, int layout, int device, void* hip_stream) {

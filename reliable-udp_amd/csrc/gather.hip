@@ -45,6 +45,10 @@
 // Only bytes inside [0, frames_bytes) of the caller's buffer are needed; a
 // rejected or dropped frame is never fetched for its own sake (the small-frame
 // image spans from the first to the last kept frame of its tile).
+//
+// ordered.hip includes this file with RUDP_GATHER_DEVICE_ONLY defined for the
+// chunk copy alone (its tiles are runs of ranks, not of frames): the kernels
+// and the launcher below are left out then.
 #include "codec_device.hpp"
 #include "internal.hpp"
 #include "scan_device.hpp"
@@ -78,6 +82,7 @@ __device__ __forceinline__ u32x4 gather_load16(const unsigned char* frames, uint
   return load16_guarded(frames, off, total);
 }
 
+#ifndef RUDP_GATHER_DEVICE_ONLY
 // ITEMS 1: a block of 256 frames holds 256 / R tiles (R a power of two), cut
 // out of the block's scan.  ITEMS 4: the block is one tile of 1024 frames.
 template <uint32_t ITEMS>
@@ -167,6 +172,8 @@ __global__ void __launch_bounds__(1024) gather_block_bases_kernel(uint64_t* sums
   }
 }
 
+#endif  // RUDP_GATHER_DEVICE_ONLY
+
 // The tile's output run [0, total) at `o`, dealt as the 16-B chunks of o's own
 // alignment over the workgroup.  LDS: windows from the staged run (`img_dw`,
 // whose byte kGatherGuard is byte gA of the aligned frames buffer); else from HBM.
@@ -222,6 +229,7 @@ __device__ __forceinline__ void gather_chunks(const GatherArgs& a, const uint64_
   }
 }
 
+#ifndef RUDP_GATHER_DEVICE_ONLY
 // One tile of a.R frames (FPT consecutive frames per thread).  Dynamic LDS:
 // frame offsets u64 [R + 1] | payload offsets in the tile u64 [R + 1] | and,
 // for the small-frame tiles (FPT > 1), guard, the staged frame run, guard.
@@ -357,5 +365,6 @@ int launch_gather_payloads(GatherArgs a, uint32_t len_hint, hipStream_t stream) 
     hipLaunchKernelGGL(gather_tile_kernel<1>, dim3((uint32_t)nt), dim3(kBlock), lds, stream, a, sums, nt);
   return (int)hipGetLastError();
 }
+#endif  // RUDP_GATHER_DEVICE_ONLY
 
 }  // namespace rudp

@@ -284,6 +284,45 @@ struct AcceptArgs {
   uint64_t* hdr;                // more than one tile: the call's scratch (set by the launcher)
 };
 
+// The reordering receiver's acceptance of a batch (window.hip).
+struct WindowArgs {
+  const uint16_t* seq;
+  const uint8_t* flags;
+  const uint32_t* chars;
+  const uint8_t* usable;        // [n], or null: every frame usable
+  uint64_t n;
+  uint64_t n_carried;           // the first frames are the ones the call before left pending (no reply)
+  uint32_t last_isn;            // above 65535: none
+  uint32_t Wc;                  // window_chars (1..1024)
+  const uint64_t* state_in;     // {expect, isn, live, 0}
+  uint64_t* state_out;          // may be state_in
+  uint8_t* accept;
+  uint32_t* rank;
+  uint32_t* carry_rank;
+  uint8_t* reply;
+  uint16_t* reply_ack;
+  uint64_t* info;               // [8]
+  uint64_t* hdr;                // the call's scratch: state and pending indices between chunks (set by the launcher)
+  uint64_t chunk, chunks;       // this launch's chunk of 1024 new frames, and how many there are (set by the launcher)
+};
+
+// Payloads out in rank order (ordered.hip).
+struct OrderedArgs {
+  const unsigned char* frames;  // moved back to a 16-B boundary by the C entry point
+  uint64_t fmis;                // distance of the caller's frames[0] from it (0..15)
+  uint64_t frames_bytes;        // size of the caller's buffer: the offset rule's limit
+  const uint64_t* frame_off;    // [n + 1]
+  const uint32_t* rank;         // [n]
+  const uint64_t* count;        // K, on the device
+  uint64_t n;
+  uint32_t skip;                // bytes left out at the head of every frame (0, 5, 7)
+  unsigned char* out;
+  uint64_t out_cap;
+  uint64_t* out_off;            // [n + 1]; [0..K] written
+  uint32_t* src;                // [n]; [0..K) written (the caller's, or scratch)
+  uint32_t* status;
+};
+
 // A datagram batch to message and replies (receive.hip): the decode's, the
 // acceptance's and the gather's arguments in one, and the reply datagrams.
 struct ReceiveArgs {
@@ -702,6 +741,14 @@ int launch_payload_chars(CharsArgs args, uint32_t len_hint, hipStream_t stream);
 // frames, else five with the tile pairs in the stream's scratch (inside a
 // ScratchCall).
 int launch_accept_inorder(AcceptArgs args, hipStream_t stream);
+// Windowed acceptance (window.hip): one launch of one workgroup per chunk of
+// 1024 new frames, the state and the pending indices between them in the
+// stream's scratch (inside a ScratchCall), and a clearing pass when there is
+// more than one chunk.
+int launch_accept_window(WindowArgs args, hipStream_t stream);
+// Payloads in rank order (ordered.hip): five launches, the tile sums and (without
+// the caller's d_src) the source table in the stream's scratch (inside a ScratchCall).
+int launch_gather_ordered(OrderedArgs args, hipStream_t stream);
 // rudp_receive (receive.hip).  The fused form: one workgroup takes the batch
 // from frames to message and replies through LDS; receive_fused_ok says whether
 // a batch takes it (n == 0 always does).  The chained form's two own steps:

@@ -29,6 +29,8 @@ ABI_VERSION = 8
 # status bits of the sync-free varlen calls (RUDP_ST_*)
 ST_LEN, ST_PAYLOAD, ST_FRAMES_CAP, ST_OFFSETS, ST_PAYLOAD_CAP = 1, 2, 4, 8, 16
 ST_PACKETS_CAP = 32  # rudp_segment_utf8: more packets than the tables hold
+ST_RANK = 64  # rudp_gather_ordered: a rank at or above the count that is not RANK_NONE
+RANK_NONE = 0xFFFFFFFF  # RUDP_RANK_NONE
 DUP_BAD_OFFSETS = 2  # rudp_dedup_window_checked: a frame whose offsets were rejected
 
 # Every symbol include/rudp.h declares (checked by tests/test_abi.py).
@@ -43,7 +45,7 @@ EXPORTS = (
     "rudp_dedup_stream_create", "rudp_dedup_stream_push", "rudp_dedup_stream_counts", "rudp_dedup_stream_destroy",
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
     "rudp_gather_payloads", "rudp_segment_utf8", "rudp_payload_chars", "rudp_accept_inorder",
-    "rudp_receive", "rudp_ack_progress", "rudp_acknowledge",
+    "rudp_receive", "rudp_ack_progress", "rudp_acknowledge", "rudp_accept_window", "rudp_gather_ordered",
 )
 ACK_EXACT, ACK_CUMULATIVE = 0, 1  # RUDP_ACK_*: the mode of rudp_ack_progress / rudp_acknowledge
 
@@ -121,6 +123,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rudp_payload_chars": [P, U64, P, U32, U64, P, I, I, P],
         "rudp_accept_inorder": [P, P, P, P, U64, U32, P, P, P, P, P, P, P, I, P],
         "rudp_receive": [P, U64, P, U32, U64, P, U32, P, ctypes.POINTER(RudpReceived), I, I, P],
+        "rudp_accept_window": [P, P, P, P, U64, U32, U32, U64, P, P, P, P, P, P, P, P, I, P],
+        "rudp_gather_ordered": [P, U64, P, U32, U64, P, P, U32, P, U64, P, P, P, I, P],
         "rudp_ack_progress": [P, P, P, P, U64, U32, U64, U32, I, U64, P, P, P, P, P, I, P],
         "rudp_acknowledge": [P, U64, P, U32, U64, P, U32, U64, U32, I, U64, P, ctypes.POINTER(RudpAcknowledged), I, I,
                              P],

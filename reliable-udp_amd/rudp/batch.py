@@ -1422,6 +1422,365 @@ def receive(frames, frame_off, layout: Union[str, int] = "rudp7", *, csum=None, 
     return Received(buf, n, H, cap)
 
 
+# ------------------------------------------------------------ the reordering receiver
+# The geometry of csrc/window.hip.
+WINDOW_CHUNK = 1024         # new frames per launch of rudp_accept_window
+WINDOW_MAX = 1024           # the largest window_chars; a call carries at most WINDOW_MAX - 1 frames
+RANK_NONE = _native.RANK_NONE
+
+
+class WindowAccepted:
+    """Result of ``accept_window``: one device buffer with cut views.
+    ``accept`` (u8 [N]: 1 delivered, 2 pending when the call ends), ``rank``
+    and ``carry_rank`` (int32 [N] holding u32 values; -1 is RUDP_RANK_NONE),
+    ``reply`` (u8 [N]), ``reply_ack`` (u16 [N]), ``state`` (int64 [4], for the
+    next call's ``state=``) and ``info`` (int64 [8]: end, ranked, msg_start,
+    characters, first_anomaly, pending, delivered, 0) as rudp_accept_window
+    defines them.  ``end``, ``count`` (ranked frames), ``msg_start``,
+    ``characters``, ``first_anomaly``, ``pending``, ``delivered`` and ``fast``
+    are read from the device on first use, one synchronization for all."""
+
+    __slots__ = ("_buf", "_n", "_lay", "_views", "_info")
+
+    def __init__(self, buf, n: int):
+        self._buf, self._n, self._lay = buf, n, WindowAccepted.layout(n)
+        self._views, self._info = {}, None
+
+    @staticmethod
+    def layout(n: int):
+        """Byte offsets in the one allocation: rank | carry_rank (u32 [n]) |
+        reply_ack (u16 [n]) | accept | reply (u8 [n]) | state (u64 [4]) | info
+        (u64 [8]); then the size."""
+        lay, at = {}, 0
+        for name, nbytes in (("rank", 4 * n), ("carry_rank", 4 * n), ("reply_ack", 2 * n), ("accept", n),
+                             ("reply", n)):
+            lay[name] = at
+            at += nbytes
+        lay["state"] = (at + 7) & ~7
+        lay["info"] = lay["state"] + 32
+        lay["size"] = lay["info"] + 64
+        return lay
+
+    def _cut(self, name, nbytes, dtype):
+        v = self._views.get(name)
+        if v is None:
+            lo = self._lay[name]
+            v = self._buf[lo:lo + nbytes]
+            v = self._views[name] = v if dtype is None else v.view(dtype)
+        return v
+
+    accept = property(lambda self: self._cut("accept", self._n, None))
+    reply = property(lambda self: self._cut("reply", self._n, None))
+
+    @property
+    def rank(self):
+        import torch
+        return self._cut("rank", 4 * self._n, torch.int32)
+
+    @property
+    def carry_rank(self):
+        import torch
+        return self._cut("carry_rank", 4 * self._n, torch.int32)
+
+    @property
+    def reply_ack(self):
+        import torch
+        return self._cut("reply_ack", 2 * self._n, torch.uint16)
+
+    @property
+    def state(self):
+        import torch
+        return self._cut("state", 32, torch.int64)
+
+    @property
+    def info(self):
+        import torch
+        return self._cut("info", 64, torch.int64)
+
+    def _host_info(self):
+        if self._info is None:
+            self._info = [int(v) for v in self.info.tolist()]
+        return self._info
+
+    end = property(lambda self: self._host_info()[0])
+    count = property(lambda self: self._host_info()[1])
+    msg_start = property(lambda self: self._host_info()[2])
+    characters = property(lambda self: self._host_info()[3])
+    first_anomaly = property(lambda self: self._host_info()[4])
+    pending = property(lambda self: self._host_info()[5])
+    delivered = property(lambda self: self._host_info()[6])
+    fast = property(lambda self: self._host_info()[4] == self._n)
+
+    def __len__(self) -> int:
+        return self._n
+
+
+def _check_window(window_chars) -> int:
+    if isinstance(window_chars, bool) or not isinstance(window_chars, int) or not 1 <= window_chars <= WINDOW_MAX:
+        raise ValueError(f"window_chars must be an int in [1, {WINDOW_MAX}], got {window_chars!r}")
+    return window_chars
+
+
+def accept_window(seq, flags, chars, *, window_chars, carried: int = 0, usable=None, state=None, last_isn=None,
+                  stream=None) -> WindowAccepted:
+    """``accept_inorder`` for a windowed sender (rudp_accept_window;
+    include/rudp.h states the rule): a frame ahead of the expected one inside
+    ``window_chars`` characters waits, is delivered when the gap before it
+    fills, and every reply is a cumulative acknowledgement.  The first
+    ``carried`` frames are the ones the previous call left pending (its
+    ``accept == 2``), presented again in its order; they get no reply.  With
+    ``window_chars=1`` the result is ``accept_inorder``'s.  The other arguments
+    as ``accept_inorder`` takes them; never waits."""
+    if not _is_torch(seq) or not _is_torch(flags) or not _is_torch(chars):
+        raise TypeError("accept_window takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    dev = seq.device
+    if dev.type != "cuda":
+        raise ValueError("accept_window runs on a HIP device")
+    Wc = _check_window(window_chars)
+    _dev_check(seq, "seq", torch.uint16, 1, dev)
+    n = seq.shape[0]
+    if isinstance(carried, bool) or not isinstance(carried, int) or not 0 <= carried <= min(n, WINDOW_MAX - 1):
+        raise ValueError(f"carried must be an int in [0, min(N, {WINDOW_MAX - 1})], got {carried!r}")
+    _int_tensor(flags, "flags", dev, n, dtypes=(torch.uint8,))
+    _int_tensor(chars, "chars", dev, n, dtypes=(torch.int32,))
+    if usable is not None:
+        _int_tensor(usable, "usable", dev, n, dtypes=(torch.uint8, torch.bool))
+    last = _check_last_isn(last_isn)
+    st = _accept_state(state, dev)
+    lay = WindowAccepted.layout(n)
+    buf = torch.empty(lay["size"], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+
+    def tab(t):
+        return t if n else None
+
+    _native.check(_native.lib().rudp_accept_window(
+        tab(seq.data_ptr()), tab(flags.data_ptr()), tab(chars.data_ptr()),
+        usable.data_ptr() if usable is not None and n else None, n, last, Wc, carried, st.data_ptr(),
+        tab(base + lay["accept"]), tab(base + lay["rank"]), tab(base + lay["carry_rank"]), tab(base + lay["reply"]),
+        tab(base + lay["reply_ack"]), base + lay["state"], base + lay["info"], dev.index or 0,
+        _stream_ptr(stream, dev)))
+    return WindowAccepted(buf, n)
+
+
+_ST_ORDERED = ((_native.ST_OFFSETS, "a ranked frame's offsets are decreasing or outside the frame buffer"),
+               (_native.ST_RANK, "a rank at or above the count is not RANK_NONE"),
+               (_native.ST_PAYLOAD_CAP, "the ranked frames do not fit the output buffer"))
+
+
+class OrderedPayloads:
+    """Result of ``gather_ordered``: ``buffer`` (u8, the caller's ``out`` or the
+    allocation), ``out_off`` (int64 [N + 1], of which [0..K] are written),
+    ``src`` (int32 [N], of which [0..K) are written: the frame of rank k),
+    ``count`` (the int64 [1] device tensor K was read from) and ``status``
+    (int32 [1], RUDP_ST_*).  ``total`` (K and the bytes, one synchronization
+    on first use) and ``payload`` (``buffer[:bytes]``) wait; nothing else does."""
+
+    __slots__ = ("buffer", "out_off", "src", "count", "status", "_total")
+
+    def __init__(self, buffer, out_off, src, count, status):
+        self.buffer, self.out_off, self.src, self.count, self.status = buffer, out_off, src, count, status
+        self._total = None
+
+    @property
+    def total(self):
+        """(K, bytes) on the host."""
+        if self._total is None:
+            import torch
+            n = self.out_off.shape[0] - 1
+            K = torch.clamp(self.count, 0, n)
+            self._total = tuple(int(v) for v in torch.cat((K, self.out_off[K])).tolist())
+        return self._total
+
+    @property
+    def payload(self):
+        return self.buffer[:min(self.total[1], self.buffer.numel())]
+
+    def check(self) -> "OrderedPayloads":
+        bits = int(self.status.item())
+        if bits:
+            msgs = [m for b, m in _ST_ORDERED if bits & b] or [f"status {bits:#x}"]
+            if bits & _native.ST_PAYLOAD_CAP:
+                msgs.append(f"{self.total[1]} bytes are needed, out has {self.buffer.numel()}")
+            raise ValueError("; ".join(msgs))
+        return self
+
+
+def gather_ordered(frames, frame_off, rank, count, *, skip: int, out=None, stream=None) -> OrderedPayloads:
+    """``gather_payloads`` with a permutation (rudp_gather_ordered): frame i
+    with ``rank[i]`` = r below K puts its bytes from ``skip`` (0, 5 or 7) on at
+    position r of the output.  ``rank``: int32 [N] holding u32 values
+    (``WindowAccepted.rank`` or ``.carry_rank``; -1 = none); ``count``: an
+    int64 [1] device tensor holding K, read on the device
+    (``WindowAccepted.info[1:2]`` or ``[5:6]``).  ``out``: u8 1-D buffer; None
+    allocates frames.numel() bytes, which always suffice.  Never waits;
+    ``check()`` on the result raises for a non-zero status."""
+    if not _is_torch(frames) or not _is_torch(frame_off) or not _is_torch(rank) or not _is_torch(count):
+        raise TypeError("gather_ordered takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    if skip not in (0, 5, 7):
+        raise ValueError(f"skip must be 0, 5 or 7, got {skip!r}")
+    dev = frames.device
+    if dev.type != "cuda":
+        raise ValueError("gather_ordered runs on a HIP device")
+    _dev_check(frames, "frames", torch.uint8, 1, dev)
+    _int_tensor(frame_off, "frame_off", dev, dtypes=(torch.int64,))
+    n = frame_off.shape[0] - 1
+    if n < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    _int_tensor(rank, "rank", dev, n, dtypes=(torch.int32,))
+    _int_tensor(count, "count", dev, 1, dtypes=(torch.int64,))
+    if out is not None:
+        _dev_check(out, "out", torch.uint8, 1, dev)
+    buffer = out if out is not None else frames.new_empty(frames.numel())
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        # out_off (i64 [n + 1]) | src (i32 [n]) | status (i32); an empty call writes nothing, so zeros
+        buf = (torch.empty if n else torch.zeros)(8 * (n + 1) + 4 * n + 4, dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+    if n:
+        _native.check(_native.lib().rudp_gather_ordered(
+            frames.data_ptr() if frames.numel() else None, frames.numel(), frame_off.data_ptr(),
+            min(frames.numel() // n, 0xFFFFFFFF), n, rank.data_ptr(), count.data_ptr(), skip,
+            buffer.data_ptr() if buffer.numel() else None, buffer.numel(), base, base + 8 * (n + 1),
+            base + 8 * (n + 1) + 4 * n, dev.index or 0, _stream_ptr(stream, dev)))
+    return OrderedPayloads(buffer, buf[:8 * (n + 1)].view(torch.int64), buf[8 * (n + 1):8 * (n + 1) + 4 * n].view(
+        torch.int32), count, buf[8 * (n + 1) + 4 * n:].view(torch.int32))
+
+
+class CarriedFrames:
+    """The frames a ``receive_window`` call left pending, whole, on the device:
+    pass it as ``carried=`` of the next call.  ``frames`` (u8) and ``frame_off``
+    (int64) are ``gather_ordered``'s output with ``skip=0``; ``csum`` the
+    sideband checksums in the same order (None without one).  ``count`` and
+    ``nbytes`` read the device once."""
+
+    __slots__ = ("_ordered", "_csum_all")
+
+    def __init__(self, ordered: OrderedPayloads, csum_all=None):
+        self._ordered, self._csum_all = ordered, csum_all
+
+    count = property(lambda self: self._ordered.total[0])
+    nbytes = property(lambda self: self._ordered.total[1])
+
+    @property
+    def frames(self):
+        return self._ordered.buffer[:self.nbytes]
+
+    @property
+    def frame_off(self):
+        return self._ordered.out_off[:self.count + 1]
+
+    @property
+    def csum(self):
+        if self._csum_all is None:
+            return None
+        import torch
+        pick = self._ordered.src[:self.count].long()
+        return self._csum_all.view(torch.int16)[pick].view(torch.uint16)  # (u16 is indexed through its i16 view)
+
+
+class ReceivedWindow:
+    """Result of ``receive_window``.  ``message`` (``OrderedPayloads``: its
+    ``payload`` is this call's part of the message in delivery order),
+    ``accepted`` (``WindowAccepted`` over carried ++ new frames), ``carried``
+    (``CarriedFrames`` for the next call), ``state`` (for the next call's
+    ``state=``), ``n_carried`` and ``n_new``.  Replies, counted in new-frame
+    indices: ``replies`` (``HeaderTable`` of n_new rows for ``pack_batch``:
+    seq 0, ack = reply_ack, flags ACK where a reply is sent), and on first use
+    (one synchronization) ``reply_index`` (int64 [R]: the new frame each reply
+    answers), ``reply_ack`` (u16 [R]) and ``reply_peer`` (int64 [R]: the new
+    frame whose source the reply goes to, the last reset at or before it;
+    n_new = the peer carried from earlier batches)."""
+
+    __slots__ = ("message", "accepted", "carried", "replies", "n_carried", "n_new", "_reset", "_reply")
+
+    def __init__(self, message, accepted, carried, replies, n_carried, n_new, reset):
+        self.message, self.accepted, self.carried, self.replies = message, accepted, carried, replies
+        self.n_carried, self.n_new, self._reset, self._reply = n_carried, n_new, reset, None
+
+    state = property(lambda self: self.accepted.state)
+
+    def _replies(self):
+        if self._reply is None:
+            import torch
+            m, n = self.n_carried, self.n_new
+            idx = torch.nonzero(self.accepted.reply[m:]).flatten()
+            pos = torch.arange(n, device=idx.device)
+            last = torch.cummax(torch.where(self._reset, pos, torch.full_like(pos, -1)), 0).values if n else pos
+            peer = last[idx]
+            ack = self.accepted.reply_ack[m:].view(torch.int16)[idx].view(torch.uint16)
+            self._reply = (idx, ack, torch.where(peer < 0, torch.full_like(peer, n), peer))
+        return self._reply
+
+    def reply_frames(self, layout: Union[str, int] = "rudp7"):
+        """u8 [R * H]: the reply datagrams, header-only frames at stride H in
+        arrival order (``pack_batch_varlen`` of seq 0, ack = reply_ack, flags
+        ACK with empty payloads)."""
+        import torch
+        ack = self.reply_ack
+        R = ack.shape[0]
+        tab = (torch.zeros_like(ack), ack, torch.full((R,), ACK, dtype=torch.uint8, device=ack.device))
+        empty = torch.empty(0, dtype=torch.uint8, device=ack.device)
+        if R == 0:
+            return empty
+        return pack_batch_varlen(tab, empty, torch.zeros(R, dtype=torch.int32, device=ack.device), layout,
+                                 want_csum=False, check=False).frames
+
+    reply_index = property(lambda self: self._replies()[0])
+    reply_ack = property(lambda self: self._replies()[1])
+    reply_peer = property(lambda self: self._replies()[2])
+    reply_count = property(lambda self: int(self._replies()[0].shape[0]))
+
+
+def receive_window(frames, frame_off, layout: Union[str, int] = "rudp7", *, window_chars, carried=None, csum=None,
+                   state=None, last_isn=None, stream=None) -> ReceivedWindow:
+    """``receive_batch`` for a windowed sender: the batch of new datagrams,
+    behind the frames the previous call left pending (``carried``: that call's
+    ``ReceivedWindow.carried``; None: none), decoded, judged by
+    ``accept_window`` and gathered in delivery order, with the pending frames
+    gathered whole for the next call: ``unpack_batch_varlen(utf8=True)`` over
+    carried ++ new -> ``keep_mask`` -> ``payload_chars`` -> ``accept_window``
+    -> ``gather_ordered`` (rank, skip = the header) -> ``gather_ordered``
+    (carry_rank, skip 0).  Reading ``carried``'s size is the one wait before
+    the call; none follows.  ``csum``: the rudp5 sideband of the new frames."""
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off):
+        raise TypeError("receive_window takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    Wc = _check_window(window_chars)
+    last = _check_last_isn(last_isn)
+    if carried is not None and not isinstance(carried, CarriedFrames):
+        raise TypeError("carried must be the `carried` of an earlier receive_window result")
+    dev = frames.device
+    n_new = frame_off.shape[0] - 1
+    if n_new < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        m = carried.count if carried is not None else 0
+        if m and (csum is None) != (carried.csum is None):
+            raise ValueError("csum must be given in every call of a transfer or in none")
+        if m:
+            all_frames = torch.cat((carried.frames, frames))
+            all_off = torch.cat((carried.frame_off, frame_off[1:] - frame_off[0] + carried.nbytes))
+            all_csum = (torch.cat((carried.csum.view(torch.int16), csum.view(torch.int16))).view(torch.uint16)
+                        if csum is not None else None)
+        else:
+            all_frames, all_off, all_csum = frames, frame_off, csum
+        dec = unpack_batch_varlen(all_frames, all_off, H, csum=all_csum, check=False, utf8=True)
+        usable = keep_mask(dec, unverified=H == 5 and csum is None)
+        chars = payload_chars(all_frames, all_off, H)
+        acc = accept_window(dec.seq, dec.flags, chars, window_chars=Wc, carried=m, usable=usable, state=state,
+                            last_isn=last)
+        msg = gather_ordered(all_frames, all_off, acc.rank, acc.info[1:2], skip=H)
+        car = gather_ordered(all_frames, all_off, acc.carry_rank, acc.info[5:6], skip=0)
+        ack = acc.reply_ack[m:]
+        replies = HeaderTable(torch.zeros_like(ack), ack, acc.reply[m:] * ACK)
+        seq64 = dec.seq.view(torch.int16)[m:].to(torch.int64) & 0xFFFF
+        reset = (usable[m:] != 0) & ((dec.flags[m:] & SYN) != 0) & (seq64 != last)
+    return ReceivedWindow(msg, acc, CarriedFrames(car, all_csum), replies, m, n_new, reset)
+
+
 # ------------------------------------------------------------ replies -> sender state
 # The geometry of csrc/acknowledge.hip (tests/test_ack_api.py holds these to the source).
 ACK_TILE = 1024            # replies per tile of rudp_ack_progress; a batch up to one tile is one launch

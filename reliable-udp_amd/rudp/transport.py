@@ -91,7 +91,7 @@ class ReliableUDP:
 
     def __init__(self, timeout=1, isn_source: Optional[Callable[[], int]] = None,
                  codec_device: Optional[str] = None, batch_recv: bool = False, batch_send: bool = False,
-                 window: int = 1, cumulative: bool = False):
+                 window: int = 1, cumulative: bool = False, reorder_window: Optional[int] = None):
         self.socket: socket
         self.retransmission_timeout = timeout
         self._draw_isn = isn_source or (lambda: random.randint(1, 5000))
@@ -108,6 +108,15 @@ class ReliableUDP:
         # device (_transmit_window); cumulative: a reply past the expected one counts (a lost reply does not stall)
         self._batch_send, self._window, self._cumulative = batch_send, window, cumulative
         self._batch_recv = batch_recv  # recv() over recvmmsg batches judged on the device (_recv_batches)
+        if reorder_window is not None:
+            if not batch_recv:
+                raise ValueError("reorder_window belongs to the batched receiver: it needs batch_recv=True")
+            if isinstance(reorder_window, bool) or not isinstance(reorder_window, int) \
+                    or not 1 <= reorder_window <= 1024:
+                raise ValueError(f"reorder_window must be an int in [1, 1024] characters, got {reorder_window!r}")
+        # recv() keeps the frames that arrive ahead of the expected one inside this many characters and
+        # answers with cumulative acks (_recv_batches_window); None: the reference's in-order receiver
+        self._reorder_window = reorder_window
         self._rx: Any = None           # its BatchReceiver, made on first use
         self._last_isn: Optional[int] = None  # the previous transfer's ISN (a repeated SYN is ignored)
         # the sender of the last SYN, kept across recv() calls as the reference
@@ -318,10 +327,50 @@ class ReliableUDP:
                 break
         return int(state[1].item()), b"".join(parts).decode(), peer
 
+    def _recv_batches_window(self):
+        """_recv_batches for a windowed sender: each batch is judged behind the
+        frames the batch before left pending (batch.receive_window: a frame
+        ahead of the expected one inside reorder_window characters waits for
+        the gap to fill), its part of the message arrives in delivery order
+        and every reply is a cumulative acknowledgement."""
+        import numpy as np
+        from . import netio
+        rx = self._batch_receiver()
+        self.socket.setblocking(True)
+        peer = self._peer
+        state = (0, 0, 1 if peer is not None else 0)
+        parts, carried = [], None
+        while True:
+            n = rx.recv(timeout_ms=-1)
+            if n == 0:
+                continue
+            res, _, _ = rx.receive_window("rudp5", window_chars=self._reorder_window, carried=carried, state=state,
+                                          last_isn=self._last_isn)
+            state, carried = res.state, res.carried
+            acc, m = res.accepted, res.n_carried
+            R = res.reply_count  # (every host read below is behind this wait)
+            if R:
+                held = netio.addr_key(*peer) if peer is not None else 0
+                src = np.append(rx.sources, np.uint64(held))  # index n: the peer carried from earlier batches
+                dst = src[res.reply_peer.cpu().numpy()]
+                netio.send_batch_to(self.socket, res.reply_frames("rudp5").cpu().numpy(),
+                                    5 * np.arange(R + 1, dtype=np.int64), dst)
+            if m <= acc.msg_start < m + n:  # a new transfer started in this batch
+                parts = []
+                peer = netio.key_addr(int(rx.sources[acc.msg_start - m]))
+                self._peer = peer
+            if peer is None:  # nothing to answer yet: nothing is kept
+                parts = []
+            elif res.message.total[1]:
+                parts.append(res.message.payload.cpu().numpy().tobytes())
+            if acc.end < m + n:
+                break
+        return int(state[1].item()), b"".join(parts).decode(), peer
+
     def recv(self) -> str:
         self.flush_recv_buffer()
         if self._batch_recv:
-            isn, text, peer = self._recv_batches()
+            isn, text, peer = self._recv_batches_window() if self._reorder_window else self._recv_batches()
             return self._finish_recv(isn, text, peer)
         isn, text, peer = 0, "", self._peer
         received = 0  # characters accepted so far (the next in-order frame is isn + received)

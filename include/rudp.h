@@ -107,6 +107,7 @@ extern "C" {
 #define RUDP_ST_PAYLOAD_CAP 16u /* gather: the kept payloads need more than payload_cap bytes */
 #define RUDP_ST_PACKETS_CAP 32u /* segment: the message makes more than max_packets packets */
 #define RUDP_ST_RANK 64u        /* gather_ordered: a rank at or above the count that is not RUDP_RANK_NONE */
+#define RUDP_ST_CARRY_CAP 128u  /* receive_window: the pending frames need more than carry_cap bytes */
 
 /* Entry points added within an ABI version, for C callers to test. */
 #define RUDP_HAS_SEGMENT_UTF8 1 /* rudp_segment_utf8 */
@@ -622,6 +623,126 @@ RUDP_API int rudp_receive(const uint8_t* d_frames, uint64_t frames_bytes, const 
                           uint32_t len_hint, uint64_t n, const uint16_t* d_csum_in_or_null, uint32_t last_isn,
                           const uint64_t* d_state_in, const rudp_received* out, int layout, int device,
                           void* hip_stream);
+
+/*
+ * The reordering receiver in one call (added within ABI 8,
+ * RUDP_HAS_RECEIVE_WINDOW): rudp_receive for a windowed sender.  One call
+ * does rudp_decode_varlen_utf8, the usable mask and rudp_payload_chars over
+ * the frames the call before left pending followed by the new datagrams,
+ * rudp_accept_window, rudp_gather_ordered twice (the message in delivery
+ * order, the frames still pending whole) and builds the reply datagrams, every
+ * output bit for bit what those calls write.  Sync-free as rudp_receive:
+ * asynchronous on hip_stream, the host never waits, temporaries come from the
+ * stream's set, usable under stream capture.  At most 1024 new datagrams with
+ * at most 32768 bytes in both buffers and 1005 bytes per frame (a recvmmsg
+ * batch of this protocol) are one launch of one workgroup that reads the
+ * frames once; larger batches join the two buffers in a temporary and run the
+ * launches of the calls above and a reply builder.
+ *
+ * Inputs.  The two sources stay separate buffers, each with its own offsets
+ * and its own bound: carried item k is d_carried[co[k], co[k + 1]) with co =
+ * d_carried_off[n_carried + 1], judged by the decode's per-frame offset rule
+ * against carried_bytes; new item j is d_frames[fo[j], fo[j + 1]) with fo =
+ * d_frame_off[n_new + 1], judged against frames_bytes.  n = n_carried + n_new;
+ * item i < n_carried is carried frame i, else new frame i - n_carried.
+ * len_hint and layout as rudp_decode_varlen_utf8; last_isn, window_chars,
+ * n_carried and d_state_in[4] as rudp_accept_window.  Sideband checksums
+ * (layout 5): item i < n_carried verifies against d_carried_csum_or_null[i],
+ * the others against d_csum_in_or_null[i - n_carried]; with n_carried > 0 the
+ * two are both given or both NULL, and both NULL with layout 7.
+ *
+ * A frame rejected by the offset rule gets ok = RUDP_OK_BAD_OFFSETS, valid =
+ * usable = chars = 0 and header fields 0; none of its bytes is read,
+ * RUDP_ST_OFFSETS is set, and it is never ranked and never pending.
+ *
+ * Outputs through *out (device pointers; n entries each unless said otherwise):
+ *   seq, ack, flags, ok, csum_out_or_null, valid
+ *                 as rudp_decode_varlen_utf8 writes them
+ *   usable        as rudp_receive defines it
+ *   chars         as rudp_payload_chars
+ *   accept, rank, carry_rank, reply, reply_ack, state_out[4] (may be
+ *   d_state_in), info[0..7]
+ *                 exactly rudp_accept_window over the n items with `usable`
+ *                 as its mask
+ *   payload, payload_cap, payload_off[n + 1], payload_src_or_null[n]
+ *                 the message: exactly rudp_gather_ordered(rank, K = info[1],
+ *                 skip = layout); payload_off[0..K] and payload_src[0..K - 1]
+ *                 are written.  When the total exceeds payload_cap,
+ *                 RUDP_ST_PAYLOAD_CAP is set, no byte of payload is written
+ *                 and payload_off[K] holds the size needed; nothing is written
+ *                 at or past the total, nor past index K of payload_off
+ *   carry_frames, carry_cap, carry_off[1024]
+ *                 the frames still pending, whole: exactly
+ *                 rudp_gather_ordered(carry_rank, P = info[5], skip = 0);
+ *                 carry_off[0..P] are written; the overflow bit is
+ *                 RUDP_ST_CARRY_CAP.  carry_frames must not overlap either
+ *                 input buffer: callers ping-pong two sets
+ *   carry_csum_or_null  u16[1023]: [k] = the input sideband checksum of the
+ *                 frame with carry rank k, written only when the input
+ *                 sidebands are given.  carry_frames, carry_off, carry_csum,
+ *                 info[5] and info[10] are the next call's d_carried,
+ *                 d_carried_off, d_carried_csum, n_carried and carried_bytes
+ *   reply_frames, reply_csum_or_null, reply_index
+ *                 as rudp_receive: R header-only frames of `layout` bytes in
+ *                 arrival order (seq 0, ack = reply_ack[i], flags 0x40, the
+ *                 checksum in-band for layout 7); reply_index[k] = i, always
+ *                 >= n_carried (carried frames get no reply).  The caller
+ *                 provides n_new * layout bytes (and n_new entries of the
+ *                 tables); nothing is written at or past R * layout
+ *   reply_peer    u64[R]: the index of the last reset (rudp_accept_inorder's
+ *                 class) at an item in [n_carried, i], or n when there is none
+ *   info          u64[12]: [8] = R; [9] = the message bytes (payload_off[K]);
+ *                 [10] = the carried bytes (carry_off[P]); [11] = 0
+ *   status        u32, required, written once: RUDP_ST_OFFSETS |
+ *                 RUDP_ST_PAYLOAD_CAP | RUDP_ST_CARRY_CAP, or 0
+ * n == 0 copies the state, writes info = {0, 0, 0, characters, 0, ... 0},
+ * status = 0 and carry_off[0] = 0, and touches nothing else.
+ * RUDP_EINVAL before any HIP call: out NULL; a layout other than 5 or 7; a
+ * sideband with layout 7, or with n_carried > 0 only one of the two given;
+ * window_chars outside [1, 1024]; n_carried > 1023; n above 2^32 - 2;
+ * d_state_in, state_out, info or status NULL; with n > 0, any table other than
+ * the _or_null ones NULL (reply_frames, reply_index and reply_peer only with
+ * n_new > 0); d_frame_off NULL with n_new > 0; d_carried_off NULL with
+ * n_carried > 0; a frames pointer NULL with its byte count > 0; payload NULL
+ * with payload_cap > 0; carry_frames NULL with carry_cap > 0.
+ */
+#define RUDP_HAS_RECEIVE_WINDOW 1
+typedef struct rudp_received_window {
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint8_t* ok;
+  uint16_t* csum_out_or_null;
+  uint8_t* valid;
+  uint8_t* usable;
+  uint32_t* chars;
+  uint8_t* accept;
+  uint32_t* rank;
+  uint32_t* carry_rank;
+  uint8_t* reply;
+  uint16_t* reply_ack;
+  uint64_t* state_out;
+  uint8_t* payload;
+  uint64_t payload_cap;
+  uint64_t* payload_off;
+  uint32_t* payload_src_or_null;
+  uint8_t* carry_frames;
+  uint64_t carry_cap;
+  uint64_t* carry_off;
+  uint16_t* carry_csum_or_null;
+  uint8_t* reply_frames;
+  uint16_t* reply_csum_or_null;
+  uint32_t* reply_index;
+  uint64_t* reply_peer;
+  uint64_t* info;
+  uint32_t* status;
+} rudp_received_window;
+RUDP_API int rudp_receive_window(const uint8_t* d_carried, uint64_t carried_bytes, const uint64_t* d_carried_off,
+                                 const uint16_t* d_carried_csum_or_null, uint64_t n_carried,
+                                 const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
+                                 const uint16_t* d_csum_in_or_null, uint64_t n_new, uint32_t len_hint,
+                                 uint32_t last_isn, uint32_t window_chars, const uint64_t* d_state_in,
+                                 const rudp_received_window* out, int layout, int device, void* hip_stream);
 
 /*
  * The sender's judgement of a reply batch (added within ABI 8,

@@ -1315,6 +1315,177 @@ int rudp_receive(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t*
   return 0;
 }
 
+int rudp_receive_window(const uint8_t* d_carried, uint64_t carried_bytes, const uint64_t* d_carried_off,
+                        const uint16_t* d_carried_csum_or_null, uint64_t n_carried, const uint8_t* d_frames,
+                        uint64_t frames_bytes, const uint64_t* d_frame_off, const uint16_t* d_csum_in_or_null,
+                        uint64_t n_new, uint32_t len_hint, uint32_t last_isn, uint32_t window_chars,
+                        const uint64_t* d_state_in, const rudp_received_window* out, int layout, int device,
+                        void* hip_stream) {
+  if (!out) return fail(RUDP_EINVAL, "rudp_receive_window: out is NULL");
+  if (layout != RUDP_LAYOUT_RUDP5 && layout != RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "unsupported layout %d (use 5 or 7)", layout);
+  if ((d_csum_in_or_null || d_carried_csum_or_null) && layout == RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "rudp_receive_window: a sideband checksum with layout 7 (its checksum is in-band)");
+  if (n_carried && !d_csum_in_or_null != !d_carried_csum_or_null)
+    return fail(RUDP_EINVAL, "rudp_receive_window: d_carried_csum and d_csum_in must be both given or both NULL");
+  if (window_chars < 1u || window_chars > 1024u)
+    return fail(RUDP_EINVAL, "rudp_receive_window: window_chars %u outside [1, 1024]", window_chars);
+  if (n_carried > 1023u)
+    return fail(RUDP_EINVAL, "rudp_receive_window: n_carried %llu above 1023", (unsigned long long)n_carried);
+  if (n_new > 0xFFFFFFFEull - n_carried)
+    return fail(RUDP_EINVAL, "rudp_receive_window: n_carried + n_new exceeds 2^32 - 2 (ranks are 32 bits)");
+  if (!d_state_in) return fail(RUDP_EINVAL, "rudp_receive_window: d_state_in is NULL");
+  if (!out->state_out) return fail(RUDP_EINVAL, "rudp_receive_window: state_out is NULL");
+  if (!out->info) return fail(RUDP_EINVAL, "rudp_receive_window: info is NULL");
+  if (!out->status) return fail(RUDP_EINVAL, "rudp_receive_window: status is NULL");
+  const uint64_t n = n_carried + n_new;
+  if (n) {
+    const struct {
+      const void* p;
+      const char* name;
+      bool needed;
+    } tables[] = {{out->seq, "seq", true}, {out->ack, "ack", true}, {out->flags, "flags", true}, {out->ok, "ok", true},
+                  {out->valid, "valid", true}, {out->usable, "usable", true}, {out->chars, "chars", true},
+                  {out->accept, "accept", true}, {out->rank, "rank", true}, {out->carry_rank, "carry_rank", true},
+                  {out->reply, "reply", true}, {out->reply_ack, "reply_ack", true},
+                  {out->payload_off, "payload_off", true}, {out->carry_off, "carry_off", true},
+                  {out->reply_frames, "reply_frames", n_new > 0}, {out->reply_index, "reply_index", n_new > 0},
+                  {out->reply_peer, "reply_peer", n_new > 0}};
+    for (const auto& t : tables)
+      if (t.needed && !t.p) return fail(RUDP_EINVAL, "rudp_receive_window: %s is NULL", t.name);
+    if (n_new && !d_frame_off) return fail(RUDP_EINVAL, "rudp_receive_window: d_frame_off is NULL");
+    if (n_carried && !d_carried_off) return fail(RUDP_EINVAL, "rudp_receive_window: d_carried_off is NULL");
+  }
+  if (!d_frames && frames_bytes) return fail(RUDP_EINVAL, "rudp_receive_window: d_frames is NULL");
+  if (!d_carried && carried_bytes) return fail(RUDP_EINVAL, "rudp_receive_window: d_carried is NULL");
+  if (!out->payload && out->payload_cap) return fail(RUDP_EINVAL, "rudp_receive_window: payload is NULL");
+  if (!out->carry_frames && out->carry_cap) return fail(RUDP_EINVAL, "rudp_receive_window: carry_frames is NULL");
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  RecvWindowArgs a{};
+  // each frames pointer moved back to a 16-B boundary: every load is an aligned block
+  const uint8_t* srcs[2] = {d_carried, d_frames};
+  for (int k = 0; k < 2; ++k) {
+    a.mis[k] = reinterpret_cast<uintptr_t>(srcs[k]) & 15u;
+    a.src[k] = srcs[k] - a.mis[k];
+  }
+  a.bytes[0] = n_carried ? carried_bytes : 0;
+  a.bytes[1] = n_new ? frames_bytes : 0;
+  a.off[0] = d_carried_off;
+  a.off[1] = d_frame_off;
+  // (without carried frames d_csum_in alone says whether there is a sideband)
+  const bool side = d_csum_in_or_null != nullptr;
+  a.csum[0] = side ? d_carried_csum_or_null : nullptr;
+  a.csum[1] = d_csum_in_or_null;
+  a.H = (uint32_t)layout;
+  a.w.seq = a.seq = out->seq;
+  a.w.flags = a.flags = out->flags;
+  a.w.chars = a.chars = out->chars;
+  a.w.usable = a.usable = out->usable;
+  a.w.n = n;
+  a.w.n_carried = n_carried;
+  a.w.last_isn = last_isn;
+  a.w.Wc = window_chars;
+  a.w.state_in = d_state_in;
+  a.w.state_out = out->state_out;
+  a.w.accept = out->accept;
+  a.w.rank = out->rank;
+  a.w.carry_rank = out->carry_rank;
+  a.w.reply = out->reply;
+  a.w.reply_ack = out->reply_ack;
+  a.w.info = a.info = out->info;
+  a.ack = out->ack;
+  a.ok = out->ok;
+  a.csum_out = out->csum_out_or_null;
+  a.valid = out->valid;
+  a.payload = out->payload;
+  a.payload_cap = out->payload_cap;
+  a.payload_off = out->payload_off;
+  a.payload_src = out->payload_src_or_null;
+  a.carry_frames = out->carry_frames;
+  a.carry_cap = out->carry_cap;
+  a.carry_off = out->carry_off;
+  a.carry_csum = out->carry_csum_or_null;
+  a.reply_frames = out->reply_frames;
+  a.reply_csum = out->reply_csum_or_null;
+  a.reply_index = out->reply_index;
+  a.reply_peer = out->reply_peer;
+  a.status = out->status;
+  ScratchCall call(s);  // the chunk's scratch and the join, until the last launch
+  if (receive_window_fused_ok(n_carried, n_new, a.bytes[0] + a.bytes[1])) {
+    rc = launch_receive_window_fused(a, s);
+    if (rc) return hip_fail((hipError_t)rc, "fused windowed receive launch");
+    return 0;
+  }
+  // The chained form: the two sources joined into one packed view in a
+  // temporary, the existing calls' launches on that view back to back on the
+  // stream, and the pass that completes what only this call has.
+  const uint64_t view = a.bytes[0] + a.bytes[1];
+  const uint64_t nb = (n + 1023u) / 1024u;
+  size_t at = 0;
+  auto take = [&at](size_t bytes) {
+    const size_t lo = at;
+    at = (at + bytes + 15u) & ~size_t(15);
+    return lo;
+  };
+  const size_t at_off = take((n + 1u) * sizeof(uint64_t)), at_sums = take(nb * sizeof(uint64_t)),
+               at_rinfo = take(8u * sizeof(uint64_t)), at_src = take(n * sizeof(uint32_t)),
+               at_words = take(4u * sizeof(uint32_t)), at_csum = take(side ? n * sizeof(uint16_t) : 0u),
+               at_view = take(view);
+  unsigned char* tmp = nullptr;
+  RUDP_HIP(stream_scratch(reinterpret_cast<void**>(&tmp), at, s, kScratchHash));
+  a.joined_off = reinterpret_cast<uint64_t*>(tmp + at_off);
+  a.sums = reinterpret_cast<uint64_t*>(tmp + at_sums);
+  a.rinfo = reinterpret_cast<uint64_t*>(tmp + at_rinfo);
+  a.carry_src = reinterpret_cast<uint32_t*>(tmp + at_src);
+  a.words = reinterpret_cast<uint32_t*>(tmp + at_words);
+  a.joined_csum = side ? reinterpret_cast<uint16_t*>(tmp + at_csum) : nullptr;
+  a.joined = tmp + at_view;
+  RUDP_HIP(hipMemsetAsync(a.words, 0, 4u * sizeof(uint32_t), s));
+  rc = launch_recv_window_join(a, s);
+  if (rc) return hip_fail((hipError_t)rc, "windowed receive join launch");
+  rc = rudp_decode_varlen_utf8(a.joined, view, a.joined_off, len_hint, n, a.joined_csum, a.seq, a.ack, a.flags, a.ok,
+                               a.csum_out, a.valid, a.words + 1, layout, device, hip_stream);
+  if (rc) return rc;
+  rc = launch_receive_usable(a.ok, a.valid, a.usable, n, s);
+  if (rc) return hip_fail((hipError_t)rc, "usable mask launch");
+  rc = rudp_payload_chars(a.joined, view, a.joined_off, len_hint, n, a.chars, layout, device, hip_stream);
+  if (rc) return rc;
+  rc = rudp_accept_window(a.seq, a.flags, a.chars, a.usable, n, last_isn, window_chars, n_carried, d_state_in,
+                          out->accept, out->rank, out->carry_rank, out->reply, out->reply_ack, out->state_out,
+                          a.info, device, hip_stream);
+  if (rc) return rc;
+  rc = rudp_gather_ordered(a.joined, view, a.joined_off, len_hint, n, out->rank, a.info + 1, (uint32_t)layout,
+                           a.payload, a.payload_cap, a.payload_off, a.payload_src, a.words + 2, device, hip_stream);
+  if (rc) return rc;
+  rc = rudp_gather_ordered(a.joined, view, a.joined_off, len_hint, n, out->carry_rank, a.info + 5, 0u,
+                           a.carry_frames, a.carry_cap, a.carry_off, a.carry_src, a.words + 3, device, hip_stream);
+  if (rc) return rc;
+  ReceiveArgs r{};
+  r.n = n;
+  r.H = (uint32_t)layout;
+  r.last_isn = last_isn;
+  r.seq = a.seq;
+  r.flags = a.flags;
+  r.usable = a.usable;
+  r.reply = out->reply;
+  r.reply_ack = out->reply_ack;
+  r.payload_off = a.joined_off;  // (the builder's own message bytes go to rinfo[6]: not this call's)
+  r.reply_frames = a.reply_frames;
+  r.reply_csum = a.reply_csum;
+  r.reply_index = a.reply_index;
+  r.reply_peer = a.reply_peer;
+  r.info = a.rinfo;
+  r.first = n_carried;
+  rc = launch_receive_replies(r, s);
+  if (rc) return hip_fail((hipError_t)rc, "reply builder launch");
+  rc = launch_recv_window_finish(a, s);
+  if (rc) return hip_fail((hipError_t)rc, "windowed receive finish launch");
+  return 0;
+}
+
 // The scalar arguments the two acknowledge entries share.
 static int ack_check_scalars(const char* who, uint32_t isn, uint64_t total_chars, uint32_t chunk_chars, int mode,
                              uint64_t sent_chars) {

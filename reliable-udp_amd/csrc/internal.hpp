@@ -358,6 +358,51 @@ struct ReceiveArgs {
   uint64_t* info;               // [8]
   uint32_t* status;
   uint64_t* tiles;              // chained form: the reply builder's tile pairs (set by the launcher)
+  uint64_t first;               // reply builder: resets count from this frame on (rudp_receive_window: n_carried)
+};
+
+// rudp_receive_window (receive_window.hip): the two sources (0: the carried
+// frames, 1: the new ones), the outputs, and what the chained form's join
+// writes for the existing launches to read.
+struct RecvWindowArgs {
+  const unsigned char* src[2];  // each moved back to a 16-B boundary by the C entry point
+  uint64_t mis[2];              // distance of the caller's pointer from it (0..15)
+  uint64_t bytes[2];            // size of the caller's buffer: each source's limit for the offset rule
+  const uint64_t* off[2];       // [n_carried + 1], [n_new + 1]
+  const uint16_t* csum[2];      // rudp5 sidebands, both or none
+  uint32_t H;
+  WindowArgs w;                 // n, n_carried, last_isn, Wc, the state, and the tables the rule reads and writes
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint8_t* ok;
+  uint16_t* csum_out;           // may be null
+  uint8_t* valid;
+  uint8_t* usable;
+  uint32_t* chars;
+  unsigned char* payload;
+  uint64_t payload_cap;
+  uint64_t* payload_off;        // [n + 1]; [0..K] written
+  uint32_t* payload_src;        // [n], may be null
+  unsigned char* carry_frames;
+  uint64_t carry_cap;
+  uint64_t* carry_off;          // [1024]; [0..P] written
+  uint16_t* carry_csum;         // [1023], may be null
+  unsigned char* reply_frames;  // [n_new * H]; R * H bytes are written
+  uint16_t* reply_csum;         // [n_new], may be null
+  uint32_t* reply_index;        // [n_new]
+  uint64_t* reply_peer;         // [n_new]
+  uint64_t* info;               // [12]
+  uint32_t* status;
+  // the chained form's temporaries (set by the C entry point): every good
+  // item's bytes back to back in one packed view, a rejected item empty
+  unsigned char* joined;        // 16-B aligned
+  uint64_t* joined_off;         // [n + 1]
+  uint16_t* joined_csum;        // [n], with sidebands
+  uint64_t* sums;               // [ceil(n / 1024)]
+  uint32_t* words;              // [0] a frame was rejected [1] the decode's status [2] the message's [3] the carry's
+  uint64_t* rinfo;              // u64[8]: the reply builder's info ([5] = R)
+  uint32_t* carry_src;          // [n]: the frame of carry rank k
 };
 
 // The sender's judgement of a reply batch (acknowledge.hip).
@@ -607,6 +652,10 @@ struct Tuning {
   // the one-workgroup fused kernel (1; 2: also past its mean frame length, for
   // sweeps) or the chain of the decode, usable, rule and closing launches (0).
   RUDP_KNOB(acknowledge_fused, 1)
+  // rudp_receive_window of at most 1024 new frames and kRwFusedBytes bytes in
+  // both buffers: the one-workgroup fused kernel (1; 2: also past its mean frame
+  // length, for sweeps) or the chain of the join and the existing launches (0).
+  RUDP_KNOB(receive_window_fused, 1)
   RUDP_KNOB(host_slots, 3)     // *_host pipeline: device staging slots (2..8)
   RUDP_KNOB(host_stage_mb, 128)  // *_host pipeline: MiB per slot (1M x 1472 B pinned: 33 ms at 128 vs 94 ms at 32)
   RUDP_KNOB(host_min_chunks, 4)  // *_host pipeline: batches over 4 MiB go as at least this many chunks (copy overlap)
@@ -675,7 +724,7 @@ class ScratchCall {
 
  private:
   friend hipError_t stream_scratch(void** ptr, size_t bytes, hipStream_t stream, int slot);
-  static constexpr int kMaxFree = 4;
+  static constexpr int kMaxFree = 8;  // (rudp_receive_window's chained form under capture takes seven)
   hipStream_t stream_ = nullptr;
   int device_ = 0;
   bool outer_ = false;    // the outermost call on this thread (a nested one is a no-op)
@@ -759,6 +808,18 @@ bool receive_fused_ok(uint64_t n, uint64_t frames_bytes);
 int launch_receive_fused(const ReceiveArgs& args, hipStream_t stream);
 int launch_receive_usable(const uint8_t* ok, const uint8_t* valid, uint8_t* usable, uint64_t n, hipStream_t stream);
 int launch_receive_replies(ReceiveArgs args, hipStream_t stream);
+// rudp_receive_window (receive_window.hip).  The fused form: one workgroup of
+// 1024 threads takes the carried and the new frames through LDS to message,
+// pending frames and replies (the chunk's scratch from the stream's set, inside
+// a ScratchCall); receive_window_fused_ok says whether a batch takes it (n == 0
+// always does).  The chained form's own steps: the join of the two sources
+// into one packed view (three launches and the copy) in front of the existing
+// launches, and behind them the pass that gives rejected items their tables,
+// gathers carry_csum and completes info and status.
+bool receive_window_fused_ok(uint64_t n_carried, uint64_t n_new, uint64_t total_bytes);
+int launch_receive_window_fused(RecvWindowArgs args, hipStream_t stream);
+int launch_recv_window_join(const RecvWindowArgs& args, hipStream_t stream);
+int launch_recv_window_finish(const RecvWindowArgs& args, hipStream_t stream);
 // rudp_ack_progress (acknowledge.hip): one launch for a batch of at most 1024
 // replies, else five with the tile maxima in the stream's scratch (inside a
 // ScratchCall).  rudp_acknowledge: the fused form (one workgroup from frames to

@@ -355,7 +355,7 @@ __device__ __forceinline__ ReplyMine reply_mine(const ReceiveArgs& a, uint64_t p
       m.rp |= 1u << j;
       ++m.cnt;
     }
-    if (acc_class(a.usable[i], a.flags[i], a.seq[i], a.last_isn) == kAccReset) {
+    if (i >= a.first && acc_class(a.usable[i], a.flags[i], a.seq[i], a.last_isn) == kAccReset) {
       m.rs |= 1u << j;
       m.last = i + 1u;
     }

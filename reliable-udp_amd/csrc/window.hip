@@ -161,8 +161,10 @@ __device__ __forceinline__ void win_write_final(const WindowArgs& a, const WinSt
   a.info[7] = 0;
 }
 
-__global__ void __launch_bounds__(kWinBlock) accept_window_kernel(WindowArgs a) {
-  __shared__ WinLds L;
+// One chunk judged by the workgroup (all kWinBlock threads call it): steps 1-8
+// above on a.seq, a.flags, a.chars and a.usable.  receive_window.hip's fused
+// kernel calls it too, on the tables it has just written (behind a barrier).
+__device__ __forceinline__ void win_judge_chunk(const WindowArgs& a, WinLds& L) {
   const uint32_t tid = threadIdx.x;
   const bool last_chunk = a.chunk + 1u == a.chunks;
   WinState s;
@@ -536,6 +538,15 @@ __global__ void __launch_bounds__(kWinBlock) accept_window_kernel(WindowArgs a) 
   }
 }
 
+// receive_window.hip includes this file with RUDP_WINDOW_DEVICE_ONLY defined
+// for the chunk's device function alone: the kernels and the launcher below
+// are left out then.
+#ifndef RUDP_WINDOW_DEVICE_ONLY
+__global__ void __launch_bounds__(kWinBlock) accept_window_kernel(WindowArgs a) {
+  __shared__ WinLds L;
+  win_judge_chunk(a, L);
+}
+
 // More than one chunk: what lies behind `end` cleared, and the ranks of the
 // frames delivered before the last reset.
 __global__ void __launch_bounds__(256) accept_window_final_kernel(WindowArgs a) {
@@ -568,5 +579,6 @@ int launch_accept_window(WindowArgs a, hipStream_t stream) {
     hipLaunchKernelGGL(accept_window_final_kernel, dim3((uint32_t)((a.n + 255u) / 256u)), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }
+#endif  // RUDP_WINDOW_DEVICE_ONLY
 
 }  // namespace rudp

@@ -30,6 +30,7 @@ ABI_VERSION = 8
 ST_LEN, ST_PAYLOAD, ST_FRAMES_CAP, ST_OFFSETS, ST_PAYLOAD_CAP = 1, 2, 4, 8, 16
 ST_PACKETS_CAP = 32  # rudp_segment_utf8: more packets than the tables hold
 ST_RANK = 64  # rudp_gather_ordered: a rank at or above the count that is not RANK_NONE
+ST_CARRY_CAP = 128  # rudp_receive_window: the pending frames need more than carry_cap bytes
 RANK_NONE = 0xFFFFFFFF  # RUDP_RANK_NONE
 DUP_BAD_OFFSETS = 2  # rudp_dedup_window_checked: a frame whose offsets were rejected
 
@@ -46,6 +47,7 @@ EXPORTS = (
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
     "rudp_gather_payloads", "rudp_segment_utf8", "rudp_payload_chars", "rudp_accept_inorder",
     "rudp_receive", "rudp_ack_progress", "rudp_acknowledge", "rudp_accept_window", "rudp_gather_ordered",
+    "rudp_receive_window",
 )
 ACK_EXACT, ACK_CUMULATIVE = 0, 1  # RUDP_ACK_*: the mode of rudp_ack_progress / rudp_acknowledge
 
@@ -72,6 +74,16 @@ class RudpReceived(ctypes.Structure):
         "reply_ack", "state_out", "payload")] + [("payload_cap", ctypes.c_uint64)] + [
         (name, ctypes.c_void_p) for name in (
             "payload_off", "reply_frames", "reply_csum", "reply_index", "reply_peer", "info", "status")]
+
+
+class RudpReceivedWindow(ctypes.Structure):
+    """struct rudp_received_window (include/rudp.h): the output pointers of rudp_receive_window."""
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "seq", "ack", "flags", "ok", "csum_out", "valid", "usable", "chars", "accept", "rank", "carry_rank",
+        "reply", "reply_ack", "state_out", "payload")] + [("payload_cap", ctypes.c_uint64)] + [
+        (name, ctypes.c_void_p) for name in ("payload_off", "payload_src", "carry_frames")] + [
+        ("carry_cap", ctypes.c_uint64)] + [(name, ctypes.c_void_p) for name in (
+            "carry_off", "carry_csum", "reply_frames", "reply_csum", "reply_index", "reply_peer", "info", "status")]
 
 
 class RudpAcknowledged(ctypes.Structure):
@@ -125,6 +137,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rudp_receive": [P, U64, P, U32, U64, P, U32, P, ctypes.POINTER(RudpReceived), I, I, P],
         "rudp_accept_window": [P, P, P, P, U64, U32, U32, U64, P, P, P, P, P, P, P, P, I, P],
         "rudp_gather_ordered": [P, U64, P, U32, U64, P, P, U32, P, U64, P, P, P, I, P],
+        "rudp_receive_window": [P, U64, P, P, U64, P, U64, P, P, U64, U32, U32, U32, P,
+                                ctypes.POINTER(RudpReceivedWindow), I, I, P],
         "rudp_ack_progress": [P, P, P, P, U64, U32, U64, U32, I, U64, P, P, P, P, P, I, P],
         "rudp_acknowledge": [P, U64, P, U32, U64, P, U32, U64, U32, I, U64, P, ctypes.POINTER(RudpAcknowledged), I, I,
                              P],

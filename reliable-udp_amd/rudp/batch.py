@@ -1781,6 +1781,269 @@ def receive_window(frames, frame_off, layout: Union[str, int] = "rudp7", *, wind
     return ReceivedWindow(msg, acc, CarriedFrames(car, all_csum), replies, m, n_new, reset)
 
 
+# The geometry of csrc/receive_window.hip (tests/test_receive_window_api.py holds these to the source).
+WINDOW_FUSED_BYTES = 32768  # rudp_receive_window: at most WINDOW_CHUNK new datagrams, this many bytes in both buffers ...
+WINDOW_FUSED_MEAN = 1005    # ... and this many per frame is one launch of one workgroup
+WINDOW_CARRY_MAX = WINDOW_MAX - 1   # the most frames a call leaves pending
+
+_ST_WINDOWED = ((_native.ST_OFFSETS, "a frame's offsets are decreasing or outside its buffer"),
+                (_native.ST_PAYLOAD_CAP, "the message does not fit the payload buffer"),
+                (_native.ST_CARRY_CAP, "the pending frames do not fit the carry buffer"))
+
+
+class CarriedWindowed:
+    """The frames a ``receive_windowed`` call left pending, whole, on the
+    device: pass it as ``carried=`` of the next call.  ``frames`` (u8, the
+    carry buffer), ``frame_off`` (int64 [1024]) and ``csum`` (u16 [1023], None
+    without a sideband) are views of that call's allocation and go to the
+    library as they are; ``count`` and ``nbytes`` come from the call's ``info``,
+    read from the device once for the whole result, on first use."""
+
+    __slots__ = ("_owner",)
+
+    def __init__(self, owner):
+        self._owner = owner
+
+    count = property(lambda self: self._owner._host_info()[5])
+    nbytes = property(lambda self: self._owner._host_info()[10])
+    frames = property(lambda self: self._owner._cut("carry", self._owner._ccap, None))
+
+    @property
+    def frame_off(self):
+        import torch
+        return self._owner._cut("carry_off", 8 * WINDOW_MAX, torch.int64)
+
+    @property
+    def csum(self):
+        import torch
+        return self._owner._cut("carry_csum", 2 * WINDOW_CARRY_MAX, torch.uint16) if self._owner._side else None
+
+
+class ReceivedWindowed:
+    """Result of ``receive_windowed``: one allocation, every member a view of it.
+
+    Over the N = n_carried + n_new items (the carried frames first): ``seq``,
+    ``ack``, ``csum`` (u16 [N]), ``flags``, ``ok``, ``valid``, ``usable`` (u8
+    [N]) and ``chars`` (int32 [N]) as ``receive`` returns them; ``accepted``
+    (a ``WindowAccepted``: accept, rank, carry_rank, reply, reply_ack, state,
+    info and its host reads); ``message`` (an ``OrderedPayloads``: this call's
+    part of the message in delivery order); ``carried`` (for the next call's
+    ``carried=``); ``state`` (for its ``state=``); ``info`` (int64 [12]) and
+    ``status`` (int32 [1]) on the device.  Replies, with ``ReceivedWindow``'s
+    meaning, counted in new-frame indices: ``reply_frames`` (u8 [R * H], the
+    datagrams at stride H in arrival order), ``reply_csum`` (u16 [R]),
+    ``reply_index`` (int64 [R]), ``reply_ack`` (u16 [R]) and ``reply_peer``
+    (int64 [R]; n_new = the peer carried from earlier batches).
+    ``reply_count``, ``message_bytes``, the host reads of ``accepted``,
+    ``message.total`` and ``carried.count`` / ``.nbytes`` share one read of
+    ``info``: one synchronization, on first use; nothing else waits."""
+
+    __slots__ = ("_buf", "_lay", "_views", "_info", "_H", "_side", "_mcap", "_ccap", "n_carried", "n_new",
+                 "accepted", "message", "carried")
+
+    def __init__(self, buf, n_carried: int, n_new: int, H: int, mcap: int, ccap: int, side: bool):
+        import torch
+        n = n_carried + n_new
+        self._buf, self._lay = buf, ReceivedWindowed.layout(n, n_new, H, mcap, ccap)
+        self._views, self._info, self._H, self._side, self._mcap, self._ccap = {}, None, H, side, mcap, ccap
+        self.n_carried, self.n_new = n_carried, n_new
+        self.accepted = WindowAccepted(buf, n)
+        self.accepted._lay = self._lay  # (the same names, this allocation's places)
+        self.message = OrderedPayloads(self._cut("payload", mcap, None),
+                                       self._cut("payload_off", 8 * (n + 1), torch.int64),
+                                       self._cut("payload_src", 4 * n, torch.int32), self.info[1:2], self.status)
+        self.carried = CarriedWindowed(self)
+
+    @staticmethod
+    def layout(n: int, n_new: int, H: int, mcap: int, ccap: int):
+        """Byte offsets in the one allocation, every array aligned to its
+        element (the two byte buffers to 16 bytes); ``size`` is the allocation's."""
+        lay, at = {}, 0
+        for name, nbytes in (("payload_off", 8 * (n + 1)), ("carry_off", 8 * WINDOW_MAX), ("reply_peer", 8 * n_new),
+                             ("state", 32), ("info", 96), ("status", 8),
+                             ("rank", 4 * n), ("carry_rank", 4 * n), ("chars", 4 * n), ("payload_src", 4 * n),
+                             ("reply_index", 4 * n_new),
+                             ("seq", 2 * n), ("ack", 2 * n), ("csum", 2 * n), ("reply_ack", 2 * n),
+                             ("reply_csum", 2 * n_new), ("carry_csum", 2 * WINDOW_MAX),
+                             ("flags", n), ("ok", n), ("valid", n), ("usable", n), ("accept", n), ("reply", n),
+                             ("reply_frames", n_new * H)):
+            lay[name] = at
+            at += nbytes
+        lay["payload"] = (at + 15) & ~15
+        lay["carry"] = (lay["payload"] + mcap + 15) & ~15
+        lay["size"] = lay["carry"] + ccap
+        return lay
+
+    def _cut(self, name, nbytes, dtype):
+        v = self._views.get(name)
+        if v is None:
+            lo = self._lay[name]
+            v = self._buf[lo:lo + nbytes]
+            v = self._views[name] = v if dtype is None else v.view(dtype)
+        return v
+
+    def _u16(self, name):
+        import torch
+        return self._cut(name, 2 * len(self), torch.uint16)
+
+    seq = property(lambda self: self._u16("seq"))
+    ack = property(lambda self: self._u16("ack"))
+    csum = property(lambda self: self._u16("csum"))
+    flags = property(lambda self: self._cut("flags", len(self), None))
+    ok = property(lambda self: self._cut("ok", len(self), None))
+    valid = property(lambda self: self._cut("valid", len(self), None))
+    usable = property(lambda self: self._cut("usable", len(self), None))
+    state = property(lambda self: self.accepted.state)
+
+    @property
+    def chars(self):
+        import torch
+        return self._cut("chars", 4 * len(self), torch.int32)
+
+    @property
+    def info(self):
+        """int64 [12] on the device: [0..7] as ``WindowAccepted.info``, then
+        reply_count, message_bytes, carried bytes, 0."""
+        import torch
+        return self._cut("info", 96, torch.int64)
+
+    @property
+    def status(self):
+        import torch
+        return self._cut("status", 4, torch.int32)
+
+    def _host_info(self):
+        if self._info is None:
+            self._info = [int(v) for v in self.info.tolist()]
+            self.accepted._info = self._info[:8]
+            self.message._total = (self._info[1], self._info[9])
+        return self._info
+
+    reply_count = property(lambda self: self._host_info()[8])
+    message_bytes = property(lambda self: self._host_info()[9])
+
+    @property
+    def reply_frames(self):
+        return self._cut("reply_frames", self.n_new * self._H, None)[:self.reply_count * self._H]
+
+    @property
+    def reply_csum(self):
+        import torch
+        return self._cut("reply_csum", 2 * self.n_new, torch.uint16)[:self.reply_count]
+
+    @property
+    def reply_index(self):
+        import torch
+        return self._cut("reply_index", 4 * self.n_new, torch.int32)[:self.reply_count].long() - self.n_carried
+
+    @property
+    def reply_ack(self):
+        import torch
+        idx = self.reply_index + self.n_carried
+        return self.accepted.reply_ack.view(torch.int16)[idx].view(torch.uint16)  # (u16 is indexed through its i16 view)
+
+    @property
+    def reply_peer(self):
+        import torch
+        peer = self._cut("reply_peer", 8 * self.n_new, torch.int64)[:self.reply_count]
+        return torch.where(peer >= len(self), torch.full_like(peer, self.n_new), peer - self.n_carried)
+
+    def check(self) -> "ReceivedWindowed":
+        """Raise ValueError if the device rejected a frame's offsets, or the
+        message or the pending frames did not fit; one synchronization."""
+        bits = int(self.status.item())
+        if bits:
+            msgs = [m for b, m in _ST_WINDOWED if bits & b] or [f"status {bits:#x}"]
+            raise ValueError("; ".join(msgs))
+        return self
+
+    def __len__(self) -> int:
+        return self.n_carried + self.n_new
+
+
+def receive_windowed(frames, frame_off, layout: Union[str, int] = "rudp7", *, window_chars, carried=None, csum=None,
+                     state=None, last_isn=None, out=None, stream=None) -> ReceivedWindowed:
+    """``receive_window`` and the reply datagrams in one library call
+    (rudp_receive_window): the new datagrams judged behind the frames the
+    previous call left pending, this call's part of the message gathered in
+    delivery order, the frames still pending gathered whole for the next call,
+    and the cumulative replies built for ``sendmmsg``, with no torch operation
+    in between: the carried and the new frames go to the library as two
+    buffers.  At most ``WINDOW_CHUNK`` new datagrams with at most
+    ``WINDOW_FUSED_BYTES`` bytes in both buffers (and ``WINDOW_FUSED_MEAN``
+    per frame) are one kernel launch.
+
+    ``frames``, ``frame_off``, ``csum``, ``state`` and ``last_isn`` as
+    ``receive`` takes them; ``window_chars`` as ``accept_window``; ``carried``:
+    the previous result's ``carried`` (None: none), whose ``count`` and
+    ``nbytes`` are that result's one host read.  ``out``: an earlier result
+    whose allocation is taken over when it is large enough (not the one
+    ``carried`` belongs to: callers ping-pong two).  Every array equals what
+    ``receive_window`` returns for the same input."""
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off):
+        raise TypeError("receive_windowed takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    Wc = _check_window(window_chars)
+    last = _check_last_isn(last_isn)
+    if carried is not None and not isinstance(carried, CarriedWindowed):
+        raise TypeError("carried must be the `carried` of an earlier receive_windowed result")
+    if out is not None and not isinstance(out, ReceivedWindowed):
+        raise TypeError("out must be an earlier receive_windowed result")
+    if out is not None and carried is not None and out is carried._owner:
+        raise ValueError("out is the result `carried` belongs to: its frames would be overwritten")
+    dev = frames.device
+    if dev.type != "cuda":
+        raise ValueError("receive_windowed runs on a HIP device")
+    _dev_check(frames, "frames", torch.uint8, 1, dev)
+    _int_tensor(frame_off, "frame_off", dev, dtypes=(torch.int64,))
+    n_new = frame_off.shape[0] - 1
+    if n_new < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    if csum is not None:
+        if H == 7:
+            raise ValueError("rudp7 carries its checksum in-band; csum is for rudp5")
+        _dev_check(csum, "csum", torch.uint16, 1, dev)
+        if csum.shape[0] != n_new:
+            raise ValueError(f"csum has {csum.shape[0]} entries for {n_new} frames")
+    m = carried.count if carried is not None else 0
+    cbytes = carried.nbytes if m else 0
+    if m and (csum is None) != (carried.csum is None):
+        raise ValueError("csum must be given in every call of a transfer or in none")
+    st = _accept_state(state, dev)
+    n, fbytes = m + n_new, frames.numel()
+    cap = fbytes + cbytes  # the message and the pending frames each fit in what came in
+    lay = ReceivedWindowed.layout(n, n_new, H, cap, cap)
+    if out is not None and out._buf.numel() >= lay["size"] and out._buf.device == dev:
+        buf = out._buf
+    else:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            buf = (torch.empty if n else torch.zeros)(lay["size"], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+
+    def tab(name, need=n):
+        return base + lay[name] if need else None
+
+    res = _native.RudpReceivedWindow(
+        seq=tab("seq"), ack=tab("ack"), flags=tab("flags"), ok=tab("ok"), csum_out=tab("csum"), valid=tab("valid"),
+        usable=tab("usable"), chars=tab("chars"), accept=tab("accept"), rank=tab("rank"),
+        carry_rank=tab("carry_rank"), reply=tab("reply"), reply_ack=tab("reply_ack"), state_out=base + lay["state"],
+        payload=tab("payload", cap), payload_cap=cap, payload_off=tab("payload_off"), payload_src=tab("payload_src"),
+        carry_frames=tab("carry", cap), carry_cap=cap, carry_off=base + lay["carry_off"],
+        carry_csum=tab("carry_csum", csum is not None), reply_frames=tab("reply_frames", n_new),
+        reply_csum=tab("reply_csum", n_new), reply_index=tab("reply_index", n_new),
+        reply_peer=tab("reply_peer", n_new), info=base + lay["info"], status=base + lay["status"])
+    side = csum is not None
+    _native.check(_native.lib().rudp_receive_window(
+        carried.frames.data_ptr() if cbytes else None, cbytes, carried.frame_off.data_ptr() if m else None,
+        carried.csum.data_ptr() if m and side else None, m,
+        frames.data_ptr() if fbytes else None, fbytes, frame_off.data_ptr(),
+        (csum.data_ptr() if n_new else carried.csum.data_ptr()) if side and n else None, n_new,
+        min(cap // n, 0xFFFFFFFF) if n else 0, last, Wc, st.data_ptr(), ctypes.byref(res), H, dev.index or 0,
+        _stream_ptr(stream, dev)))
+    return ReceivedWindowed(buf, m, n_new, H, cap, cap, side)
+
+
 # ------------------------------------------------------------ replies -> sender state
 # The geometry of csrc/acknowledge.hip (tests/test_ack_api.py holds these to the source).
 ACK_TILE = 1024            # replies per tile of rudp_ack_progress; a batch up to one tile is one launch

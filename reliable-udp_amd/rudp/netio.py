@@ -299,6 +299,42 @@ class BatchReceiver:
             t.record_stream(cur)
         return res, d_frames, d_off
 
+    def receive_windowed(self, layout="rudp5", *, window_chars, carried=None, csum=None, state=None, last_isn=None,
+                         out=None, stream=None):
+        """H2D of the received frames as ``receive()`` does it (the same slot and
+        event bookkeeping), then ``batch.receive_windowed``: ``receive_window``
+        and the reply datagrams in one library call, the carried and the new
+        frames as two buffers.  Never waits for the device beyond the size of
+        ``carried`` (the previous result's one host read).
+
+        Returns ``(ReceivedWindowed, d_frames, d_frame_off)``; reply k answers
+        new datagram ``res.reply_index[k]`` and goes to
+        ``self.sources[res.reply_peer[k]]``, or to the peer carried from earlier
+        batches where ``reply_peer[k]`` is the datagram count."""
+        import torch
+        s = stream if stream is not None else self.stream
+        k, n = self._slot, self.count
+        if k < 0:
+            raise RuntimeError("receive_windowed() before any recv()")
+        total = int(self._off_t[k][n])
+        s.wait_stream(torch.cuda.current_stream(self.device))  # e.g. csum or state written by the caller
+        with torch.cuda.stream(s):
+            d_frames = torch.empty((total,), dtype=torch.uint8, device=self.device)
+            d_off = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+            d_frames.copy_(self._frames_t[k][:total], non_blocking=True)
+            d_off.copy_(self._off_t[k][:n + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(s)
+            self._copied[k] = ev
+            res = _batch.receive_windowed(d_frames, d_off, layout, window_chars=window_chars, carried=carried,
+                                          csum=csum, state=state, last_isn=last_isn, out=out, stream=s)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(s)
+        # allocated on `s`, used on the caller's stream from here on
+        for t in (d_frames, d_off, res._buf):  # the result's members are views of one buffer
+            t.record_stream(cur)
+        return res, d_frames, d_off
+
     def acknowledge(self, layout="rudp5", *, isn, total_chars, chunk=1, state=None, mode="exact", sent=None,
                     csum=None, stream=None):
         """H2D of the received reply datagrams as ``receive()`` does it (the same

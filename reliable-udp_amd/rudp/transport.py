@@ -91,7 +91,8 @@ class ReliableUDP:
 
     def __init__(self, timeout=1, isn_source: Optional[Callable[[], int]] = None,
                  codec_device: Optional[str] = None, batch_recv: bool = False, batch_send: bool = False,
-                 window: int = 1, cumulative: bool = False, reorder_window: Optional[int] = None):
+                 window: int = 1, cumulative: bool = False, reorder_window: Optional[int] = None,
+                 reorder_fused: bool = False):
         self.socket: socket
         self.retransmission_timeout = timeout
         self._draw_isn = isn_source or (lambda: random.randint(1, 5000))
@@ -117,6 +118,11 @@ class ReliableUDP:
         # recv() keeps the frames that arrive ahead of the expected one inside this many characters and
         # answers with cumulative acks (_recv_batches_window); None: the reference's in-order receiver
         self._reorder_window = reorder_window
+        if reorder_fused and reorder_window is None:
+            raise ValueError("reorder_fused belongs to the reordering receiver: it needs reorder_window")
+        # each batch judged, gathered and answered in one library call (batch.receive_windowed); False:
+        # the chain of calls (batch.receive_window)
+        self._reorder_fused = bool(reorder_fused)
         self._rx: Any = None           # its BatchReceiver, made on first use
         self._last_isn: Optional[int] = None  # the previous transfer's ISN (a repeated SYN is ignored)
         # the sender of the last SYN, kept across recv() calls as the reference
@@ -332,7 +338,9 @@ class ReliableUDP:
         frames the batch before left pending (batch.receive_window: a frame
         ahead of the expected one inside reorder_window characters waits for
         the gap to fill), its part of the message arrives in delivery order
-        and every reply is a cumulative acknowledgement."""
+        and every reply is a cumulative acknowledgement.  With reorder_fused
+        a batch is one library call (batch.receive_windowed) and one wait, at
+        reply_count: the sizes of the pending frames come out of the same read."""
         import numpy as np
         from . import netio
         rx = self._batch_receiver()
@@ -344,8 +352,9 @@ class ReliableUDP:
             n = rx.recv(timeout_ms=-1)
             if n == 0:
                 continue
-            res, _, _ = rx.receive_window("rudp5", window_chars=self._reorder_window, carried=carried, state=state,
-                                          last_isn=self._last_isn)
+            receive = rx.receive_windowed if self._reorder_fused else rx.receive_window
+            res, _, _ = receive("rudp5", window_chars=self._reorder_window, carried=carried, state=state,
+                                last_isn=self._last_isn)
             state, carried = res.state, res.carried
             acc, m = res.accepted, res.n_carried
             R = res.reply_count  # (every host read below is behind this wait)
@@ -353,8 +362,8 @@ class ReliableUDP:
                 held = netio.addr_key(*peer) if peer is not None else 0
                 src = np.append(rx.sources, np.uint64(held))  # index n: the peer carried from earlier batches
                 dst = src[res.reply_peer.cpu().numpy()]
-                netio.send_batch_to(self.socket, res.reply_frames("rudp5").cpu().numpy(),
-                                    5 * np.arange(R + 1, dtype=np.int64), dst)
+                frames = res.reply_frames if self._reorder_fused else res.reply_frames("rudp5")
+                netio.send_batch_to(self.socket, frames.cpu().numpy(), 5 * np.arange(R + 1, dtype=np.int64), dst)
             if m <= acc.msg_start < m + n:  # a new transfer started in this batch
                 parts = []
                 peer = netio.key_addr(int(rx.sources[acc.msg_start - m]))

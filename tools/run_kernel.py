@@ -1,6 +1,6 @@
 """Run one codec op repeatedly on one shape, for rocprofv3 captures.
 
-usage: python tools/run_kernel.py --op encode|decode|roundtrip|encode_varlen|decode_varlen|utf8|dedup|gather|chars|accept|receive
+usage: python tools/run_kernel.py --op encode|decode|roundtrip|encode_varlen|decode_varlen|utf8|dedup|gather|chars|accept|receive|receive_window
           [--L 1472] [--n 1048576]
           [--layout rudp7] [--steps 20] [--ragged] [--tune 51=1,52=2]
 Prints the HIP-event time per launch so it can be set beside the profiler's
@@ -57,7 +57,8 @@ def mixed_text_payloads(n, L, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", choices=["encode", "decode", "decode_copy", "roundtrip", "encode_varlen",
-                                     "decode_varlen", "utf8", "dedup", "gather", "chars", "accept", "receive"],
+                                     "decode_varlen", "utf8", "dedup", "gather", "chars", "accept", "receive",
+                                     "receive_window"],
                     default="encode",
                     help="utf8: strict UTF-8 check of the fixed-stride frames (bench leg "
                          "utf8_validate_1Mx1472); dedup: the proxy's 500-deep retransmission check "
@@ -67,7 +68,9 @@ def main():
                          "frames (rudp_payload_chars); accept: the receiver's in-order acceptance over "
                          "the decoded table of those frames (rudp_accept_inorder); receive: those frames "
                          "to message and replies in one call (rudp_receive; the synth tables are no "
-                         "transfer, so little is accepted: the launches are what is looked at)")
+                         "transfer, so little is accepted: the launches are what is looked at); receive_window: "
+                         "the same frames through the reordering receiver's one call (rudp_receive_window, "
+                         "a window of 8 characters, nothing carried)")
     ap.add_argument("--L", type=int, default=1472)
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--layout", default="rudp7")
@@ -116,7 +119,8 @@ def main():
     del ctypes
 
     vsets = []
-    if args.op.endswith("varlen") or args.op in ("dedup", "gather", "chars", "accept", "receive"):
+    if args.op.endswith("varlen") or args.op in ("dedup", "gather", "chars", "accept", "receive",
+                                                      "receive_window"):
         for tab, pay, fr in sets:
             if args.ragged:
                 g = torch.Generator(device=dev).manual_seed(7)
@@ -153,6 +157,9 @@ def main():
                 batch.accept_inorder(dec.seq, dec.flags, achars[i % nsets])
             elif args.op == "receive":
                 batch.receive(res.frames, res.frame_off, args.layout, csum=res.csum if H == 5 else None)
+            elif args.op == "receive_window":
+                batch.receive_windowed(res.frames, res.frame_off, args.layout, window_chars=8,
+                                       csum=res.csum if H == 5 else None)
             elif args.op == "gather":
                 batch.gather_payloads(res.frames, res.frame_off, args.layout, keep=gkeep, out=gbuf, check=False)
             else:

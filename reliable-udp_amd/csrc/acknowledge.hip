@@ -38,9 +38,9 @@
 //   valid and pointer up to the end it finds.  It writes d_state_out and d_info;
 //   5. zeroes past the end and the count of valid replies.
 // A batch of one tile runs the five steps in one launch, and the fused form of
-// rudp_acknowledge runs them on a tile it decoded into LDS itself.
-#include "codec_device.hpp"
-#include "internal.hpp"
+// rudp_acknowledge runs them on a tile it decoded into LDS itself, out of the
+// frame image of frame_image_device.hpp.
+#include "frame_image_device.hpp"
 #include "scan_device.hpp"
 
 namespace RUDP_NS {
@@ -56,7 +56,6 @@ constexpr uint32_t kAckHdr = 8;                   // scratch words before the ti
 // asking, and a frame is decoded by one lane.
 constexpr uint32_t kAckFusedBytes = 32768;
 constexpr uint32_t kAckFusedMeanFrame = 261;
-constexpr uint32_t kAckBadOff = 0xFFFFFFFFu;  // an offset past frames_bytes, in the LDS copy
 
 struct AckSeed {
   uint64_t p, L, last, done;
@@ -106,28 +105,6 @@ __device__ __forceinline__ bool ack_valid(const AckArgs& a, uint32_t us, uint32_
   return d - p >= L && d <= a.sent && (d % a.C == 0 || d == a.T);
 }
 
-// Exclusive prefix maximum of one u64 per thread over the block (all threads call it).
-__device__ inline uint64_t ack_exclusive_max(uint64_t x, uint64_t* total, uint64_t* s_wave) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  uint64_t incl = x;
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(incl, d, 64);
-    if (lane >= d && y > incl) incl = y;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  uint64_t ex = __shfl_up(incl, 1, 64);
-  if (lane == 0) ex = 0;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-  for (uint32_t w = 0; w < nwaves; ++w) {
-    if (w < wave) before = ack_max64(before, s_wave[w]);
-    all = ack_max64(all, s_wave[w]);
-  }
-  __syncthreads();  // s_wave may be reused by the caller
-  *total = all;
-  return ack_max64(before, ex);
-}
-
 // Replies [p0, p0 + Rv) into LDS, coalesced.
 __device__ __forceinline__ void ack_load(const AckArgs& a, AckLds& L, uint64_t p0, uint32_t Rv) {
   for (uint32_t k = threadIdx.x; k < Rv; k += kBlock) {
@@ -146,7 +123,7 @@ __device__ inline uint64_t ack_tile_max(const AckArgs& a, AckLds& L, uint32_t Rv
     if (k < Rv) agg = ack_max64(agg, ack_cand(a, L.us[k], L.fl[k], L.ack[k]));
   }
   uint64_t total;
-  ack_exclusive_max(agg, &total, L.wv);
+  block_exclusive_max(agg, L.wv, &total);
   return total;
 }
 
@@ -162,8 +139,7 @@ __device__ inline void ack_scan(const AckArgs& a, AckLds& L, uint64_t p0, uint32
     cand[j] = k < Rv ? ack_cand(a, L.us[k], L.fl[k], L.ack[k]) : 0ull;
     agg = ack_max64(agg, cand[j]);
   }
-  uint64_t total;
-  uint64_t s = ack_max64(base, ack_exclusive_max(agg, &total, L.wv));
+  uint64_t s = ack_max64(base, block_exclusive_max(agg, L.wv));
   unsigned long long e_min = a.n, a_min = a.n;
 #pragma unroll
   for (uint32_t j = 0; j < kAckFpt; ++j) {
@@ -386,8 +362,7 @@ __global__ void __launch_bounds__(kBlock) ack_bases_kernel(uint64_t* hdr, uint64
   const uint64_t lo = threadIdx.x * per < nt ? threadIdx.x * per : nt, hi = lo + per < nt ? lo + per : nt;
   uint64_t mine = 0;
   for (uint64_t i = lo; i < hi; ++i) mine = ack_max64(mine, tiles[i]);
-  uint64_t total;
-  uint64_t run = ack_max64(hdr[0], ack_exclusive_max(mine, &total, wv));
+  uint64_t run = ack_max64(hdr[0], block_exclusive_max(mine, wv));
   for (uint64_t i = lo; i < hi; ++i) {
     const uint64_t v = tiles[i];
     tiles[i] = run;
@@ -527,7 +502,7 @@ int launch_ack_usable(const uint8_t* ok, uint8_t* usable, uint64_t n, hipStream_
 
 struct AckFusedLds {
   AckLds t;
-  uint32_t fo[kAckTile + 1];  // frame offsets in the image (kAckBadOff: past the buffer)
+  uint32_t fo[kAckTile + 1];  // frame offsets in the image (kImgBadOff: past the buffer)
   uint16_t seq[kAckTile];
   uint32_t bad;               // a frame failed the offset rule
   // the aligned buffer from the 16-B boundary below d_frames, and window16_dw's reach past it
@@ -550,22 +525,8 @@ __global__ void __launch_bounds__(kBlock) acknowledge_fused_kernel(AcknowledgeAr
 
   // 1. the buffer into LDS once, and its offsets
   {
-    const uint32_t img_bytes = a.frames_bytes ? (uint32_t)(a.fmis + a.frames_bytes) : 0u;
-    const uint32_t nvec = (img_bytes + 15u) >> 4;
-    u32x4* dst = reinterpret_cast<u32x4*>(S.img);
-    for (uint32_t v0 = tid; v0 < nvec; v0 += 4u * kBlock) {
-      u32x4 q[4];
-#pragma unroll
-      for (uint32_t u = 0; u < 4; ++u)
-        if (v0 + u * kBlock < nvec) q[u] = load16_guarded(a.frames, 16ull * (v0 + u * kBlock), img_bytes);
-#pragma unroll
-      for (uint32_t u = 0; u < 4; ++u)
-        if (v0 + u * kBlock < nvec) dst[v0 + u * kBlock] = q[u];
-    }
-    for (uint32_t k = tid; k <= n; k += kBlock) {
-      const uint64_t o = a.frame_off[k];
-      S.fo[k] = o <= a.frames_bytes ? (uint32_t)(o + a.fmis) : kAckBadOff;
-    }
+    image_load(S.img, a.frames, a.frames_bytes ? (uint32_t)(a.fmis + a.frames_bytes) : 0u, kBlock);
+    image_offsets(S.fo, a.frame_off, n, a.frames_bytes, a.fmis, kBlock);
     if (tid == 0) {
       L.e_min = r.n;
       L.a_min = r.n;
@@ -576,61 +537,24 @@ __global__ void __launch_bounds__(kBlock) acknowledge_fused_kernel(AcknowledgeAr
 
   // 2. every frame by one lane: the decode's outputs and usable
   {
-    const uint32_t* dw = S.img;
     uint32_t any_bad = 0;
 #pragma unroll 1
     for (uint32_t j = 0; j < kAckFpt; ++j) {
       const uint32_t q = j * kBlock + tid;
       if (q >= n) break;
-      const uint32_t fs = S.fo[q], fe = S.fo[q + 1u];
-      uint32_t seq = 0, ack = 0, fl = 0, ok = RUDP_OK_BAD_OFFSETS, cs = 0;
-      if (fs == kAckBadOff || fe == kAckBadOff || fs > fe) {
-        any_bad = 1;  // rejected: nothing of it is read
-      } else {
-        const uint32_t F = fe - fs, ps = fs + (uint32_t)H;
-        uint32_t ev = 0, od = 0;  // byte sums at even / odd image offsets
-        if (fe > ps) {  // the payload's dwords, the edge ones masked to it
-          const uint32_t w0 = ps >> 2, w1 = (fe - 1u) >> 2;
-          for (uint32_t w = w0; w <= w1; ++w) {
-            uint32_t v = dw[w];
-            if (w == w0 || w == w1) {
-              const int lo = (int)ps - (int)(4u * w), hi = (int)fe - (int)(4u * w);
-              v &= (uint32_t)byte_mask(lo < 0 ? 0 : lo, hi < 4 ? hi : 4);
-            }
-            ev = even_bytes_acc(v, ev);
-            od = odd_bytes_acc(v, od);
-          }
-        }
-        const uint32_t sum = (fs & 1u) ? (ev + (od << 8)) : ((ev << 8) + od);
-        const u32x4 h = window16_dw(dw, fs);
-        const uint32_t b0 = h.x & 0xFFu, b1 = (h.x >> 8) & 0xFFu, b2 = (h.x >> 16) & 0xFFu, b3 = h.x >> 24,
-                       b4 = h.y & 0xFFu, b5 = (h.y >> 8) & 0xFFu, b6 = (h.y >> 16) & 0xFFu;
-        if (F < (uint32_t)H) {  // short frame: fields truncated as utils/packet.py:31 slices them
-          const uint32_t c0 = F > 0 ? b0 : 0u, c1 = F > 1 ? b1 : 0u, c2 = F > 2 ? b2 : 0u, c3 = F > 3 ? b3 : 0u,
-                         c4 = F > 4 ? b4 : 0u;
-          seq = F >= 2 ? (c0 << 8) | c1 : c0;
-          ack = F >= 4 ? (c2 << 8) | c3 : c2;
-          fl = c4;
-          ok = RUDP_OK_SHORT;
-        } else {
-          seq = (b0 << 8) | b1;
-          ack = (b2 << 8) | b3;
-          fl = b4;
-          cs = packet_csum(sum, seq, ack, fl);
-          if (H == 7) ok = cs == ((b5 << 8) | b6) ? RUDP_OK_GOOD : RUDP_OK_BAD_CSUM;
-          else ok = a.csum_in ? (cs == a.csum_in[q] ? RUDP_OK_GOOD : RUDP_OK_BAD_CSUM) : RUDP_OK_UNVERIFIED;
-        }
-      }
-      const uint32_t us = ok == RUDP_OK_GOOD || ok == RUDP_OK_UNVERIFIED;
-      a.seq[q] = (uint16_t)seq;
-      a.ack[q] = (uint16_t)ack;
-      a.flags[q] = (uint8_t)fl;
-      a.ok[q] = (uint8_t)ok;
-      if (a.csum_out) a.csum_out[q] = (uint16_t)cs;
+      const FrameDecode d = image_decode_frame<H, false>(S.img, S.fo[q], S.fo[q + 1u], a.csum_in != nullptr,
+                                                         [&] { return (uint32_t)a.csum_in[q]; });
+      any_bad |= d.ok == RUDP_OK_BAD_OFFSETS;
+      const uint32_t us = d.ok == RUDP_OK_GOOD || d.ok == RUDP_OK_UNVERIFIED;
+      a.seq[q] = (uint16_t)d.seq;
+      a.ack[q] = (uint16_t)d.ack;
+      a.flags[q] = (uint8_t)d.fl;
+      a.ok[q] = (uint8_t)d.ok;
+      if (a.csum_out) a.csum_out[q] = (uint16_t)d.cs;
       a.usable[q] = (uint8_t)us;
-      S.seq[q] = (uint16_t)seq;
-      L.ack[q] = (uint16_t)ack;
-      L.fl[q] = (uint8_t)fl;
+      S.seq[q] = (uint16_t)d.seq;
+      L.ack[q] = (uint16_t)d.ack;
+      L.fl[q] = (uint8_t)d.fl;
       L.us[q] = (uint8_t)us;
     }
     if (any_bad) atomicOr(&S.bad, 1u);

@@ -46,43 +46,17 @@
 // rejected or dropped frame is never fetched for its own sake (the small-frame
 // image spans from the first to the last kept frame of its tile).
 //
-// ordered.hip includes this file with RUDP_GATHER_DEVICE_ONLY defined for the
-// chunk copy alone (its tiles are runs of ranks, not of frames): the kernels
-// and the launcher below are left out then.
-#include "codec_device.hpp"
-#include "internal.hpp"
+// The chunk copy (gather_chunks) and gather_plen are in gather_device.hpp,
+// which ordered.hip shares (its tiles are runs of ranks, not of frames); this
+// file has the kernels and the launcher.
+#include "gather_device.hpp"
 #include "scan_device.hpp"
 
 namespace RUDP_NS {
 
-constexpr uint32_t kGatherGuard = 32;             // LDS bytes before and after a staged run (window16_dw's reach)
-constexpr int kGatherBadShift = 63;               // a tile sum's bit 63: a frame of the block failed the offset rule
-constexpr uint64_t kGatherSumMask = (1ull << kGatherBadShift) - 1ull;
-// Totals saturate here (no payload buffer is this large): sums of frames that
-// overlap (valid pairs of unordered offsets) cannot wrap past payload_cap.
-constexpr uint64_t kGatherSat = 1ull << 53;
 constexpr uint32_t kGatherSmallFpt = 4;           // small frames: frames per thread (tiles of 1024)
 constexpr uint32_t kGatherTileBytes = 98304;      // larger frames: hinted frame bytes per tile
 
-// Payload bytes frame [fo0, fo1) contributes; *bad set when its offsets are rejected.
-__device__ __forceinline__ uint64_t gather_plen(uint64_t fo0, uint64_t fo1, uint64_t lim, uint32_t H, bool kept,
-                                                uint32_t* bad) {
-  if (fo0 > fo1 || fo1 > lim) {
-    *bad = 1u;
-    return 0;
-  }
-  const uint64_t f = fo1 - fo0;
-  return kept && f > H ? f - H : 0ull;
-}
-
-// load16_guarded with a plain (cached) load: the HBM path reads every aligned
-// block from two neighbouring lanes, and the second read is to hit in cache.
-__device__ __forceinline__ u32x4 gather_load16(const unsigned char* frames, uint64_t off, uint64_t total) {
-  if (off + 16 <= total) return *reinterpret_cast<const u32x4*>(frames + off);
-  return load16_guarded(frames, off, total);
-}
-
-#ifndef RUDP_GATHER_DEVICE_ONLY
 // ITEMS 1: a block of 256 frames holds 256 / R tiles (R a power of two), cut
 // out of the block's scan.  ITEMS 4: the block is one tile of 1024 frames.
 template <uint32_t ITEMS>
@@ -172,64 +146,6 @@ __global__ void __launch_bounds__(1024) gather_block_bases_kernel(uint64_t* sums
   }
 }
 
-#endif  // RUDP_GATHER_DEVICE_ONLY
-
-// The tile's output run [0, total) at `o`, dealt as the 16-B chunks of o's own
-// alignment over the workgroup.  LDS: windows from the staged run (`img_dw`,
-// whose byte kGatherGuard is byte gA of the aligned frames buffer); else from HBM.
-template <bool LDS>
-__device__ __forceinline__ void gather_chunks(const GatherArgs& a, const uint64_t* s_fo, const uint64_t* s_po,
-                                              uint32_t Rv, uint64_t total, unsigned char* o, const uint32_t* img_dw,
-                                              uint64_t gA) {
-  const uint32_t lead = (uint32_t)(-(uintptr_t)o) & 15u;  // bytes before the run's first aligned chunk
-  const uint64_t nch = total > lead ? (total - lead + 15u) / 16u + 1u : 1u;  // chunk 0 is the head [0, lead)
-  const uint64_t src0 = a.fmis + a.H;
-  const uint64_t lim = a.fmis + a.frames_bytes;
-  for (uint64_t c = threadIdx.x; c < nch; c += kBlock) {
-    // chunk c covers run bytes [x, x + 16) of which [b_lo, b_hi) are the tile's
-    const int64_t x = c == 0 ? (int64_t)lead - 16 : (int64_t)(lead + 16u * (c - 1u));
-    const int b_lo = x < 0 ? (int)-x : 0;
-    const int b_hi = (uint64_t)(x + 16) <= total ? 16 : (int)((int64_t)total - x);
-    if (b_hi <= b_lo) continue;
-    const uint64_t y = (uint64_t)(x + b_lo);
-    // the frame of run byte y: the last q with s_po[q] <= y (s_po[0] = 0 <= y < total = s_po[Rv])
-    uint32_t q = 0, qh = Rv;
-    while (qh - q > 1u) {
-      const uint32_t m = (q + qh) >> 1;
-      if (s_po[m] <= y) q = m; else qh = m;
-    }
-    uint64_t j = y - s_po[q];
-    uint64_t lo = 0, hi = 0;
-    for (int b = b_lo; b < b_hi; ++q, j = 0) {
-      const uint64_t left = s_po[q + 1] - s_po[q] - j;  // (0: a dropped, rejected or empty frame)
-      if (left == 0) continue;
-      const int take = left < (uint64_t)(b_hi - b) ? (int)left : b_hi - b;
-      // chunk byte b is payload q's byte j, byte s_fo[q] + src0 + j of the aligned buffer
-      u32x4 w;
-      if (LDS) {
-        w = window16_dw(img_dw, kGatherGuard + (uint32_t)(s_fo[q] + src0 - gA) + (uint32_t)j - (uint32_t)b);
-      } else {
-        const int64_t pos = (int64_t)(s_fo[q] + src0 + j) - b;  // (>= -15)
-        const int64_t blk = pos & ~(int64_t)15;
-        const uint32_t sh = (uint32_t)(pos & 15);
-        const u32x4 zero = {0u, 0u, 0u, 0u};
-        const u32x4 w0 = blk >= 0 ? gather_load16(a.frames, (uint64_t)blk, lim) : zero;
-        const u32x4 w1 = sh ? gather_load16(a.frames, (uint64_t)(blk + 16), lim) : zero;
-        w = funnel32(w0, w1, sh);
-      }
-      lo |= lo64(w) & byte_mask(b, b + take);
-      hi |= hi64(w) & byte_mask(b - 8, b + take - 8);
-      b += take;
-    }
-    if (b_lo == 0 && b_hi == 16) {
-      __builtin_nontemporal_store(make_u32x4(lo, hi), reinterpret_cast<u32x4*>(o + x));
-    } else {
-      for (int b = b_lo; b < b_hi; ++b) o[x + b] = (unsigned char)(b < 8 ? lo >> (8 * b) : hi >> (8 * (b - 8)));
-    }
-  }
-}
-
-#ifndef RUDP_GATHER_DEVICE_ONLY
 // One tile of a.R frames (FPT consecutive frames per thread).  Dynamic LDS:
 // frame offsets u64 [R + 1] | payload offsets in the tile u64 [R + 1] | and,
 // for the small-frame tiles (FPT > 1), guard, the staged frame run, guard.
@@ -365,6 +281,5 @@ int launch_gather_payloads(GatherArgs a, uint32_t len_hint, hipStream_t stream) 
     hipLaunchKernelGGL(gather_tile_kernel<1>, dim3((uint32_t)nt), dim3(kBlock), lds, stream, a, sums, nt);
   return (int)hipGetLastError();
 }
-#endif  // RUDP_GATHER_DEVICE_ONLY
 
 }  // namespace rudp

@@ -16,8 +16,8 @@
 // The grids are sized by n, the bound of K; tiles and threads past K leave.
 // Ranks that repeat below K leave src[] with one of the frames: every index
 // it holds is below n, so every read and write stays in bounds.
-#define RUDP_GATHER_DEVICE_ONLY 1
-#include "gather.hip"
+#include "gather_device.hpp"
+#include "scan_device.hpp"
 
 namespace RUDP_NS {
 

@@ -16,17 +16,18 @@
 //                 with aligned 16-B guarded loads from the boundary at or below
 //                 its pointer, the second starting on the next 16-B boundary
 //                 of the image; per item its start and end in the image
-//                 (kRwBad: rejected by its source's offset rule);
+//                 (kImgBadOff: rejected by its source's offset rule);
 //              2. one lane per item (at most two per thread): header, RFC 1071
-//                 sum, UTF-8 verdict, lead bytes, as receive.hip's fused kernel;
+//                 sum, UTF-8 verdict, lead bytes (image_decode_frame of
+//                 frame_image_device.hpp, as receive.hip's fused kernel);
 //                 the decode tables, usable and chars;
-//              3. the chunk judged by win_judge_chunk on the tables just
+//              3. the chunk judged by win_judge_chunk (window_device.hpp) on the tables just
 //                 written (behind a barrier), anomaly walk included;
 //              4. the frame of every rank and of every carry rank (two LDS
 //                 source tables), and two scans of their lengths in rank order
 //                 (the message without the header, the pending frames whole);
 //              5. both gathers out of the image as 16-B chunks of the output's
-//                 own alignment (receive.hip's edge rule with a rank -> item
+//                 own alignment (image_copy_ranked with a rank -> item
 //                 indirection: no store covers a byte outside [0, total));
 //              6. the replies, two consecutive items per thread, the last
 //                 reset counted from n_carried on;
@@ -40,9 +41,8 @@
 //            builder with its resets counted from n_carried on), and one pass
 //            that gives the rejected items their tables, gathers carry_csum
 //            and completes info and status.
-#define RUDP_WINDOW_DEVICE_ONLY 1
-#include "window.hip"
-#include "utf8_device.hpp"
+#include "frame_image_device.hpp"
+#include "window_device.hpp"
 
 namespace RUDP_NS {
 
@@ -56,7 +56,6 @@ constexpr uint32_t kRwFusedBytes = 32768;
 // 83 us; 125 x 261 B: 37 against 85; profiles/r13/receive_window.json).  Longer
 // means are not measured and chain.
 constexpr uint32_t kRwFusedMeanFrame = 1005;
-constexpr uint32_t kRwBad = 0xFFFFFFFFu;  // an item rejected by the offset rule, in the LDS tables
 constexpr uint32_t kRwCarryMax = kWinNew - 1u;  // pending frames a call can leave (distinct starts inside the window)
 
 // Item i's source, its index there, and whether its offsets pass that
@@ -69,24 +68,11 @@ __device__ __forceinline__ bool rw_item(const RecvWindowArgs& a, uint64_t i, uin
   return *o0 <= *o1 && *o1 <= a.bytes[*s];
 }
 
-template <int H>
-__device__ __forceinline__ void rw_put_reply(const RecvWindowArgs& a, uint32_t slot, uint32_t i, uint32_t ack,
-                                             uint32_t r) {
-  const uint32_t c = packet_csum(0u, 0u, ack, 0x40u);
-  const uint64_t h = pack_header<H>(0u, ack, 0x40u, c);
-  unsigned char* o = a.reply_frames + (uint64_t)slot * (uint64_t)H;
-#pragma unroll
-  for (int b = 0; b < H; ++b) o[b] = (unsigned char)(h >> (8 * b));
-  if (a.reply_csum) a.reply_csum[slot] = (uint16_t)c;
-  a.reply_index[slot] = i;
-  a.reply_peer[slot] = r ? (uint64_t)(r - 1u) : a.w.n;
-}
-
 // ------------------------------------------------------------------ fused form
 
 struct RwLds {
   WinLds win;
-  uint32_t is[kWinItems], ie[kWinItems];  // every item's start and end in the image (kRwBad: rejected)
+  uint32_t is[kWinItems], ie[kWinItems];  // every item's start and end in the image (kImgBadOff: rejected)
   uint32_t mo[kWinItems + 1];             // message offsets in rank order
   uint32_t co[kWinNew + 1];               // the pending frames' offsets in carry-rank order
   uint16_t msrc[kWinItems];               // the item of every rank (kWinNil: none)
@@ -110,7 +96,7 @@ __device__ inline uint32_t rw_rank_offsets(const RwLds& S, const uint16_t* src, 
     len[u] = 0;
     if (k < K) {
       const uint32_t p = src[k];
-      if (p != kWinNil && S.is[p] != kRwBad) {
+      if (p != kWinNil && S.is[p] != kImgBadOff) {
         const uint32_t F = S.ie[p] - S.is[p];
         len[u] = F > skip ? F - skip : 0u;
       }
@@ -133,40 +119,6 @@ __device__ inline uint32_t rw_rank_offsets(const RwLds& S, const uint16_t* src, 
     out_off[K] = total;
   }
   return total;
-}
-
-// The K ranked items' bytes past `skip`, [0, total), out of the image to `o`,
-// dealt as the 16-B chunks of o's own alignment: a whole chunk is one 16-B
-// store, the partial chunk at either end goes bytewise.
-__device__ inline void rw_copy_ranked(const RwLds& S, const uint32_t* po, const uint16_t* src, uint32_t K,
-                                      uint32_t total, uint32_t skip, unsigned char* o) {
-  const unsigned char* img = reinterpret_cast<const unsigned char*>(S.img);
-  const uint32_t lead = (uint32_t)(-(uintptr_t)o) & 15u;  // bytes before the first aligned chunk
-  const uint32_t nch = total > lead ? (total - lead + 15u) / 16u + 1u : 1u;  // chunk 0 is the head [0, lead)
-  for (uint32_t c = threadIdx.x; c < nch; c += kWinBlock) {
-    const int x = c == 0 ? (int)lead - 16 : (int)(lead + 16u * (c - 1u));
-    const int b_lo = x < 0 ? -x : 0;
-    const int b_hi = (uint32_t)(x + 16) <= total ? 16 : (int)total - x;
-    if (b_hi <= b_lo) continue;
-    uint32_t y = (uint32_t)(x + b_lo);
-    // the rank of output byte y: the last q with po[q] <= y (po[0] = 0 <= y < total = po[K])
-    uint32_t q = 0, qh = K;
-    while (qh - q > 1u) {
-      const uint32_t m = (q + qh) >> 1;
-      if (po[m] <= y) q = m; else qh = m;
-    }
-    uint64_t lo = 0, hi = 0;
-    for (int b = b_lo; b < b_hi; ++b, ++y) {
-      while (po[q + 1u] <= y) ++q;  // (y < po[K]: stops at a rank with bytes, so src[q] is an item)
-      const uint64_t v = img[S.is[src[q]] + skip + (y - po[q])];
-      if (b < 8) lo |= v << (8 * b); else hi |= v << (8 * (b - 8));
-    }
-    if (b_lo == 0 && b_hi == 16) {
-      *reinterpret_cast<u32x4*>(o + x) = make_u32x4(lo, hi);
-    } else {
-      for (int b = b_lo; b < b_hi; ++b) o[x + b] = (unsigned char)(b < 8 ? lo >> (8 * b) : hi >> (8 * (b - 8)));
-    }
-  }
 }
 
 template <int H>
@@ -197,7 +149,7 @@ __global__ void __launch_bounds__(kWinBlock) receive_window_fused_kernel(RecvWin
         S.is[p] = base + (uint32_t)o0;
         S.ie[p] = base + (uint32_t)o1;
       } else {
-        S.is[p] = S.ie[p] = kRwBad;
+        S.is[p] = S.ie[p] = kImgBadOff;
         any_bad = 1;
       }
     }
@@ -206,68 +158,20 @@ __global__ void __launch_bounds__(kWinBlock) receive_window_fused_kernel(RecvWin
     if (any_bad) atomicOr(&S.bad, 1u);
 
     // 2. every item by one lane: the decode's outputs, usable and chars
-    const uint32_t* dw = S.img;
-    const unsigned char* ibytes = reinterpret_cast<const unsigned char*>(S.img);
 #pragma unroll 1
     for (uint32_t q = tid; q < n; q += kWinBlock) {
-      const uint32_t fs = S.is[q], fe = S.ie[q];
-      uint32_t seq = 0, ack = 0, fl = 0, ok = RUDP_OK_BAD_OFFSETS, cs = 0, valid = 0, ch = 0;
-      if (fs != kRwBad) {  // (a rejected item: nothing of it is read)
-        const uint32_t F = fe - fs, ps = fs + (uint32_t)H;
-        uint32_t ev = 0, od = 0, hib = 0;  // byte sums at even / odd image offsets; high bits of the payload
-        if (fe > ps) {  // the payload's dwords, the edge ones masked to it
-          const uint32_t w0 = ps >> 2, w1 = (fe - 1u) >> 2;
-          for (uint32_t w = w0; w <= w1; ++w) {
-            uint32_t v = dw[w], lanes = 0xFu;
-            if (w == w0 || w == w1) {
-              const int lo = (int)ps - (int)(4u * w), hi = (int)fe - (int)(4u * w);
-              const int l0 = lo < 0 ? 0 : lo, h0 = hi < 4 ? hi : 4;
-              v &= (uint32_t)byte_mask(l0, h0);
-              lanes = ((1u << h0) - 1u) & ~((1u << l0) - 1u);
-            }
-            hib |= v;
-            ev = even_bytes_acc(v, ev);
-            od = odd_bytes_acc(v, od);
-            ch += __popc(lead4(v) & lanes);
-          }
-        }
-        valid = (hib & 0x80808080u) && utf8_check_bytes(ps, fe, [&](uint32_t i) { return (uint32_t)ibytes[i]; }) ? 0u
-                                                                                                                 : 1u;
-        const uint32_t sum = (fs & 1u) ? (ev + (od << 8)) : ((ev << 8) + od);
-        const u32x4 h = window16_dw(dw, fs);
-        const uint32_t b0 = h.x & 0xFFu, b1 = (h.x >> 8) & 0xFFu, b2 = (h.x >> 16) & 0xFFu, b3 = h.x >> 24,
-                       b4 = h.y & 0xFFu, b5 = (h.y >> 8) & 0xFFu, b6 = (h.y >> 16) & 0xFFu;
-        if (F < (uint32_t)H) {  // short frame: fields truncated as utils/packet.py:31 slices them
-          const uint32_t c0 = F > 0 ? b0 : 0u, c1 = F > 1 ? b1 : 0u, c2 = F > 2 ? b2 : 0u, c3 = F > 3 ? b3 : 0u,
-                         c4 = F > 4 ? b4 : 0u;
-          seq = F >= 2 ? (c0 << 8) | c1 : c0;
-          ack = F >= 4 ? (c2 << 8) | c3 : c2;
-          fl = c4;
-          ok = RUDP_OK_SHORT;
-        } else {
-          seq = (b0 << 8) | b1;
-          ack = (b2 << 8) | b3;
-          fl = b4;
-          cs = packet_csum(sum, seq, ack, fl);
-          if (H == 7) {
-            ok = cs == ((b5 << 8) | b6) ? RUDP_OK_GOOD : RUDP_OK_BAD_CSUM;
-          } else if (a.csum[1]) {
-            const uint32_t want = q < nc ? a.csum[0][q] : a.csum[1][q - nc];
-            ok = cs == want ? RUDP_OK_GOOD : RUDP_OK_BAD_CSUM;
-          } else {
-            ok = RUDP_OK_UNVERIFIED;
-          }
-        }
-      }
-      const uint32_t us = (ok == RUDP_OK_GOOD || ok == RUDP_OK_UNVERIFIED) && valid == 1u;
-      a.seq[q] = (uint16_t)seq;
-      a.ack[q] = (uint16_t)ack;
-      a.flags[q] = (uint8_t)fl;
-      a.ok[q] = (uint8_t)ok;
-      if (a.csum_out) a.csum_out[q] = (uint16_t)cs;
-      a.valid[q] = (uint8_t)valid;
+      const FrameDecode d = image_decode_frame<H, true>(S.img, S.is[q], S.ie[q], a.csum[1] != nullptr, [&] {
+        return (uint32_t)(q < nc ? a.csum[0][q] : a.csum[1][q - nc]);
+      });
+      const uint32_t us = (d.ok == RUDP_OK_GOOD || d.ok == RUDP_OK_UNVERIFIED) && d.valid == 1u;
+      a.seq[q] = (uint16_t)d.seq;
+      a.ack[q] = (uint16_t)d.ack;
+      a.flags[q] = (uint8_t)d.fl;
+      a.ok[q] = (uint8_t)d.ok;
+      if (a.csum_out) a.csum_out[q] = (uint16_t)d.cs;
+      a.valid[q] = (uint8_t)d.valid;
       a.usable[q] = (uint8_t)us;
-      a.chars[q] = ch;
+      a.chars[q] = d.chars;
     }
     __syncthreads();  // the tables are final in global memory
   }
@@ -303,6 +207,7 @@ __global__ void __launch_bounds__(kWinBlock) receive_window_fused_kernel(RecvWin
 
   // 6. the replies: two consecutive items per thread
   {
+    const ReplyOut out{a.reply_frames, a.reply_csum, a.reply_index, a.reply_peer, a.w.n};
     uint32_t rp = 0, rs = 0, cnt = 0, ra[2] = {0, 0};
 #pragma unroll
     for (uint32_t u = 0; u < 2; ++u) {
@@ -318,12 +223,12 @@ __global__ void __launch_bounds__(kWinBlock) receive_window_fused_kernel(RecvWin
     }
     uint32_t R = 0;
     uint32_t slot = block_exclusive_scan32(cnt, &R, S.sw32);
-    uint32_t r = win_exclusive_max(rs ? 2u * tid + (rs >> 1 ? 1u : 0u) + 1u : 0u, S.sw32);
+    uint32_t r = block_exclusive_max(rs ? 2u * tid + (rs >> 1 ? 1u : 0u) + 1u : 0u, S.sw32);
 #pragma unroll
     for (uint32_t u = 0; u < 2; ++u) {
       const uint32_t p = 2u * tid + u;
       if (rs & (1u << u)) r = p + 1u;
-      if (rp & (1u << u)) rw_put_reply<H>(a, slot++, p, ra[u], r);
+      if (rp & (1u << u)) put_reply<H>(out, slot++, p, ra[u], r);
     }
     if (tid == 0) a.info[8] = R;
   }
@@ -331,8 +236,11 @@ __global__ void __launch_bounds__(kWinBlock) receive_window_fused_kernel(RecvWin
 
   // 5. both gathers out of the image;  7. carry_csum, info and status
   const bool mfits = mtotal <= a.payload_cap, cfits = ctotal <= a.carry_cap;
-  if (mfits && mtotal) rw_copy_ranked(S, S.mo, S.msrc, K, mtotal, (uint32_t)H, a.payload);
-  if (cfits && ctotal) rw_copy_ranked(S, S.co, S.csrc, P, ctotal, 0u, a.carry_frames);
+  if (mfits && mtotal)
+    image_copy_ranked(S.img, S.mo, K, mtotal, a.payload, kWinBlock,
+                      [&](uint32_t q) { return S.is[S.msrc[q]] + (uint32_t)H; });
+  if (cfits && ctotal)
+    image_copy_ranked(S.img, S.co, P, ctotal, a.carry_frames, kWinBlock, [&](uint32_t q) { return S.is[S.csrc[q]]; });
   if (a.carry_csum && a.csum[1]) {
     for (uint32_t k = tid; k < P; k += kWinBlock) {
       const uint32_t p = S.csrc[k];

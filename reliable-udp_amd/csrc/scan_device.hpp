@@ -1,5 +1,7 @@
-// Block-wide scan shared by the offset scan (scan.hip) and the small-frame
-// varlen encode, which folds the scan's last pass into its own tile (varlen.hip).
+// Block-wide scans shared by the offset scan (scan.hip), the small-frame varlen
+// encode, which folds the scan's last pass into its own tile (varlen.hip), and
+// the receiver- and sender-side kernels: exclusive sums, and the exclusive
+// prefix maximum.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +36,31 @@ __device__ inline uint64_t block_exclusive_scan(uint64_t x, uint64_t* total, uin
   __syncthreads();  // s_wave may be reused by the caller
   *total = all;
   return before + incl - x;
+}
+
+// Exclusive prefix maximum of one value per thread over the block (uint32_t or
+// uint64_t; all threads call it); *total, when asked for, the block's maximum.
+template <typename T>
+__device__ inline T block_exclusive_max(T x, T* s_wave, T* total = nullptr) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  T incl = x;
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const T y = __shfl_up(incl, d, 64);
+    if (lane >= d && y > incl) incl = y;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  T ex = __shfl_up(incl, 1, 64);
+  if (lane == 0) ex = 0;
+  __syncthreads();
+  T before = 0, all = 0;
+  for (uint32_t w = 0; w < nwaves; ++w) {
+    const T v = s_wave[w];
+    if (w < wave && v > before) before = v;
+    if (v > all) all = v;
+  }
+  __syncthreads();  // s_wave may be reused by the caller
+  if (total) *total = all;
+  return before > ex ? before : ex;
 }
 
 // The same for values whose block total fits 32 bits (lengths of at most a

@@ -40,8 +40,17 @@ def _hipcc() -> str:
 
 
 def _newest_header() -> float:
+    # Everything a source may include: csrc/*.hpp and include/*.h.  No .hip
+    # includes a .hip (tests/test_build_deps.py holds the sources to that), so
+    # a source's own mtime and this one cover all it depends on.
     hdrs = list(CSRC.glob("*.hpp")) + list(INCLUDE.glob("*.h"))
     return max((h.stat().st_mtime for h in hdrs), default=0.0)
+
+
+def _stale(src_mtime: float, hdr_mtime: float, obj_mtime: float | None, force: bool) -> bool:
+    """Whether an object must be rebuilt: forced, missing, or older than its
+    source or the newest header."""
+    return force or obj_mtime is None or obj_mtime < max(src_mtime, hdr_mtime)
 
 
 def _build_one(lib: Path, objdir: Path, defines, force: bool, verbose: bool, hipcc: str, hdr_time: float,
@@ -56,7 +65,7 @@ def _build_one(lib: Path, objdir: Path, defines, force: bool, verbose: bool, hip
     def compile_one(src: str) -> Path:
         s = CSRC / src
         o = objdir / (Path(src).stem + ".o")
-        if force or not o.exists() or o.stat().st_mtime < max(s.stat().st_mtime, hdr_time):
+        if _stale(s.stat().st_mtime, hdr_time, o.stat().st_mtime if o.exists() else None, force):
             if s.suffix == ".cpp":  # host-only C++ (no HIP): plain g++
                 cmd = [shutil.which("g++") or "g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-fvisibility=hidden",
                        f"-I{INCLUDE}", *defines, "-c", str(s), "-o", str(o)]

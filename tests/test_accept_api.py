@@ -172,7 +172,7 @@ def test_python_geometry_matches_the_kernel_source():
     """batch.ACCEPT_TILE / ACCEPT_BASES / CHARS_BLOCK / payload_chars_lanes restate
     accept.hip's launch geometry (the GPU tests put their edge cases there)."""
     csrc = REPO / "reliable-udp_amd" / "csrc"
-    hip = (csrc / "accept.hip").read_text()
+    hip = (csrc / "accept.hip").read_text() + (csrc / "accept_device.hpp").read_text()
     block = int(re.search(r"constexpr int kBlock = (\d+);", (csrc / "codec_device.hpp").read_text()).group(1))
     fpt = int(re.search(r"constexpr uint32_t kAccFpt = (\d+);", hip).group(1))
     assert re.search(r"constexpr uint32_t kAccTile = kBlock \* kAccFpt;", hip)

@@ -114,7 +114,7 @@ def test_python_geometry_matches_the_kernel_source():
             "         (knob == 2 || frames_bytes <= (uint64_t)kRecvFusedMeanFrame * n);") in hip
     assert batch.RECV_TILE == batch.ACCEPT_TILE  # (test_accept_api.py holds that one to accept.hip's kAccTile)
     # the fused form's LDS stays within what a workgroup gets without asking
-    acc = (csrc / "accept.hip").read_text()
+    acc = (csrc / "accept_device.hpp").read_text()
     assert "uint64_t pk[kAccTile];" in acc and "uint32_t img[(kRecvFusedBytes + 16u + 32u) / 4u];" in hip
     T = batch.RECV_TILE
     lds = (4 + 2 + 2 + 4 + 8) * T + 256 + 2 * 4 * (T + 1) + 64 + batch.RECV_FUSED_BYTES + 48

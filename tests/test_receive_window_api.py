@@ -149,7 +149,7 @@ def test_python_geometry_matches_the_kernel_source():
     choice of form (the GPU tests put their edge cases there)."""
     csrc = REPO / "reliable-udp_amd" / "csrc"
     hip = (csrc / "receive_window.hip").read_text()
-    win = (csrc / "window.hip").read_text()
+    win = (csrc / "window.hip").read_text() + (csrc / "window_device.hpp").read_text()
     assert int(re.search(r"constexpr uint32_t kRwFusedBytes = (\d+);", hip).group(1)) == batch.WINDOW_FUSED_BYTES
     assert int(re.search(r"constexpr uint32_t kRwFusedMeanFrame = (\d+);", hip).group(1)) == batch.WINDOW_FUSED_MEAN
     assert int(re.search(r"constexpr uint32_t kWinNew = (\d+);", win).group(1)) == batch.WINDOW_CHUNK

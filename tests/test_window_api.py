@@ -205,7 +205,7 @@ def test_python_argument_checks():
 
 def test_geometry_constants_restate_the_source():
     from conftest import PKG
-    hip = (PKG / "csrc" / "window.hip").read_text()
+    hip = (PKG / "csrc" / "window_device.hpp").read_text()
     assert f"kWinNew = {batch.WINDOW_CHUNK};" in hip and "uint16_t ring[1024];" in hip
 
 

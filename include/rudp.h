@@ -19,7 +19,10 @@
  * of the one's-complement sum of the frame taken as big-endian 16-bit words
  * with the checksum field (rudp7) zero and an odd tail zero-padded.  In the
  * rudp5 layout the frame carries no checksum field; the value is returned as
- * a sideband u16 per packet.
+ * a sideband u16 per packet.  A decode verifies by recomputing that value and
+ * comparing it with the carried one (the in-band field, or the sideband
+ * entry), so a frame that carries 0xFFFF where the checksum is 0x0000, or the
+ * reverse, is RUDP_OK_BAD_CSUM.
  *
  * Conventions
  *  - Buffers are caller-owned; the library never allocates or frees them.

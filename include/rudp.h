@@ -535,6 +535,80 @@ RUDP_API int rudp_gather_ordered(const uint8_t* d_frames, uint64_t frames_bytes,
                                  uint32_t* d_src_or_null, uint32_t* d_status, int device, void* hip_stream);
 
 /*
+ * One datagram batch judged for many peers (added within ABI 8,
+ * RUDP_HAS_ACCEPT_FLOWS): a server's recvmmsg batch carries datagrams of many
+ * concurrent transfers; every transfer is judged by rudp_accept_inorder's
+ * rule, independently, in one launch, with all per-peer state in a device
+ * table.  Sync-free: asynchronous on hip_stream, the host never waits, no
+ * temporaries, usable under stream capture.
+ *
+ * d_seq, d_flags, d_chars, d_usable_or_null and n as rudp_accept_inorder takes
+ * them; d_flow[i] (u32) is the slot of datagram i's peer.  d_states is
+ * u64[n_flows][4], read and written in place; a row is {expect, isn, live,
+ * last_isn + 1}, word 3 == 0 meaning "no previous transfer", so an all-zero
+ * table is a table of fresh flows.  Only the rows of slots that occur in the
+ * batch are read or written; the call does no work proportional to n_flows.
+ *
+ * Per flow the rule is exactly rudp_accept_inorder's, applied to the flow's
+ * datagrams in arrival order with the row as d_state_in and word 3 - 1 as
+ * last_isn (none when word 3 is 0 or above 65536).  A datagram with d_flow[i]
+ * == RUDP_FLOW_NONE is ignored as an unusable one is; one with d_flow[i] >=
+ * n_flows is ignored too and sets RUDP_ST_FLOW.  An ignored datagram gets
+ * every output 0, rank RUDP_RANK_NONE, and touches no row.
+ *
+ * The flow's first accepted FIN ends that flow's transfer (arrival index
+ * end_f): its later datagrams in this call are not judged (outputs 0), and
+ * the flow turns over on the device, its row becomes {0, 0, 0, isn + 1}: a
+ * closed flow that accepts and answers nothing until a SYN arrives whose seq
+ * differs from that ISN.  (live = 0 after the end is this library's choice;
+ * the single-peer receiver keeps answering its old peer.)  A flow that does
+ * not end gets {expect, isn, live, word 3 unchanged}.
+ *
+ * Per-datagram outputs, n entries each, in arrival order: d_accept, d_keep,
+ * d_reply, d_reply_ack as rudp_accept_inorder defines them, per flow (keep:
+ * accepted, at or after the flow's last reset at or before its end, and at or
+ * before its end); d_rank[i] (u32): a kept datagram's position in the
+ * flow-major message order (ascending slot, arrival order within a slot),
+ * else RUDP_RANK_NONE.  With d_rank, d_info + 1 as d_count and skip = layout,
+ * rudp_gather_ordered writes all flows' message pieces back to back.
+ *
+ * Grouping outputs, A = the distinct valid slots of the batch:
+ *   d_order[n]        u32: the arrival indices, flow-major; the datagrams
+ *                     without a valid slot follow, in arrival order
+ *   d_order_off[0..A] u32: where each active flow's run starts in d_order;
+ *                     [A]: where the flowless ones start (provide n + 1)
+ *   d_flow_info       u64[A][8], ascending by slot (provide n rows): [0] slot
+ *                     [1] end (arrival index; n: none) [2] accepted datagrams
+ *                     [3] msg_start (arrival index of the last reset at or
+ *                     before the end; n: none) [4] characters so far (expect -
+ *                     isn when live, else 0; before the turn-over) [5] isn
+ *                     (before the turn-over) [6] kept datagrams [7] rank base
+ *                     (the kept datagrams of the flows before it)
+ *   d_info            u64[8]: [0] A [1] K, the kept total [2] R, the replies
+ *                     [3] flows that ended [4] datagrams without a valid slot
+ *                     [5] flows the kernel judged sequentially (a diagnostic,
+ *                     not part of the contract) [6..7] 0
+ *   *d_status         required: 0 or RUDP_ST_FLOW
+ * Nothing is written past index A of d_order_off or past row A - 1 of
+ * d_flow_info.  n == 0 writes d_info = 0 and *d_status = 0 and touches nothing
+ * else.  n > RUDP_FLOWS_MAX_BATCH returns RUDP_ENOTSUP (a recvmmsg batch never
+ * exceeds it).  RUDP_EINVAL before any HIP call: d_states, d_info or d_status
+ * NULL; n_flows 0 or above 2^32 - 2; with n > 0, any other pointer except
+ * d_usable_or_null NULL.
+ */
+#define RUDP_HAS_ACCEPT_FLOWS 1
+#define RUDP_FLOW_NONE 0xFFFFFFFFu
+#define RUDP_FLOWS_MAX_BATCH 1024u
+#define RUDP_ST_FLOW 256u   /* a d_flow[i] at or above n_flows that is not RUDP_FLOW_NONE */
+RUDP_API int rudp_accept_flows(const uint16_t* d_seq, const uint8_t* d_flags, const uint32_t* d_chars,
+                               const uint8_t* d_usable_or_null, const uint32_t* d_flow, uint64_t n,
+                               uint64_t* d_states, uint64_t n_flows,
+                               uint8_t* d_accept, uint8_t* d_keep, uint8_t* d_reply, uint16_t* d_reply_ack,
+                               uint32_t* d_rank, uint32_t* d_order, uint32_t* d_order_off,
+                               uint64_t* d_flow_info, uint64_t* d_info, uint32_t* d_status,
+                               int device, void* hip_stream);
+
+/*
  * A datagram batch to message and replies in one call (added within ABI 8,
  * RUDP_HAS_RECEIVE): what the reference's recv() loop makes of the datagrams
  * of one recvmmsg (utils/reliableUDP.py:97-137) and the send_ack packets it

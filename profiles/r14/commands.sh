@@ -12,3 +12,8 @@
 # build's median.
 # kernel_resources.md: hipcc -Rpass-analysis=kernel-resource-usage, same flags, parent -> this.
 # bench.json: python bench.py --gpus 1 --steps 20 --warmup 5, the headline leg of both builds.
+#
+# rudp_accept_flows (many peers in one batch), one MI355X, the product library with a build
+# of the parent commit (git worktree, python reliable-udp_amd/rudp/_build.py) beside it:
+#   python tools/flows_probe.py --parent <parent build>/librudp.so --out profiles/r14/flows_probe.json
+# flows_probe.json: medians over 11 rounds of 200 back-to-back calls, the forms in rotation.

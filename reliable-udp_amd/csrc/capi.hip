@@ -1182,6 +1182,60 @@ int rudp_accept_window(const uint16_t* d_seq, const uint8_t* d_flags, const uint
   return 0;
 }
 
+int rudp_accept_flows(const uint16_t* d_seq, const uint8_t* d_flags, const uint32_t* d_chars,
+                      const uint8_t* d_usable_or_null, const uint32_t* d_flow, uint64_t n, uint64_t* d_states,
+                      uint64_t n_flows, uint8_t* d_accept, uint8_t* d_keep, uint8_t* d_reply, uint16_t* d_reply_ack,
+                      uint32_t* d_rank, uint32_t* d_order, uint32_t* d_order_off, uint64_t* d_flow_info,
+                      uint64_t* d_info, uint32_t* d_status, int device, void* hip_stream) {
+  if (!d_states) return fail(RUDP_EINVAL, "rudp_accept_flows: d_states is NULL");
+  if (!d_info) return fail(RUDP_EINVAL, "rudp_accept_flows: d_info is NULL");
+  if (!d_status) return fail(RUDP_EINVAL, "rudp_accept_flows: d_status is NULL");
+  if (n_flows < 1u || n_flows > 0xFFFFFFFEull)
+    return fail(RUDP_EINVAL, "rudp_accept_flows: n_flows %llu outside [1, 2^32 - 2]", (unsigned long long)n_flows);
+  if (n > RUDP_FLOWS_MAX_BATCH)
+    return fail(RUDP_ENOTSUP, "rudp_accept_flows: n %llu exceeds RUDP_FLOWS_MAX_BATCH (%u datagrams, one recvmmsg batch)",
+                (unsigned long long)n, RUDP_FLOWS_MAX_BATCH);
+  if (n) {
+    if (!d_seq) return fail(RUDP_EINVAL, "rudp_accept_flows: d_seq is NULL");
+    if (!d_flags) return fail(RUDP_EINVAL, "rudp_accept_flows: d_flags is NULL");
+    if (!d_chars) return fail(RUDP_EINVAL, "rudp_accept_flows: d_chars is NULL");
+    if (!d_flow) return fail(RUDP_EINVAL, "rudp_accept_flows: d_flow is NULL");
+    if (!d_accept) return fail(RUDP_EINVAL, "rudp_accept_flows: d_accept is NULL");
+    if (!d_keep) return fail(RUDP_EINVAL, "rudp_accept_flows: d_keep is NULL");
+    if (!d_reply) return fail(RUDP_EINVAL, "rudp_accept_flows: d_reply is NULL");
+    if (!d_reply_ack) return fail(RUDP_EINVAL, "rudp_accept_flows: d_reply_ack is NULL");
+    if (!d_rank) return fail(RUDP_EINVAL, "rudp_accept_flows: d_rank is NULL");
+    if (!d_order) return fail(RUDP_EINVAL, "rudp_accept_flows: d_order is NULL");
+    if (!d_order_off) return fail(RUDP_EINVAL, "rudp_accept_flows: d_order_off is NULL");
+    if (!d_flow_info) return fail(RUDP_EINVAL, "rudp_accept_flows: d_flow_info is NULL");
+  }
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  FlowsArgs a{};
+  a.seq = d_seq;
+  a.flags = d_flags;
+  a.chars = d_chars;
+  a.usable = d_usable_or_null;
+  a.flow = d_flow;
+  a.n = n;
+  a.states = d_states;
+  a.n_flows = n_flows;
+  a.accept = d_accept;
+  a.keep = d_keep;
+  a.reply = d_reply;
+  a.reply_ack = d_reply_ack;
+  a.rank = d_rank;
+  a.order = d_order;
+  a.order_off = d_order_off;
+  a.flow_info = d_flow_info;
+  a.info = d_info;
+  a.status = d_status;
+  rc = launch_accept_flows(a, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "flows acceptance launch");
+  return 0;
+}
+
 int rudp_gather_ordered(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
                         uint32_t len_hint, uint64_t n, const uint32_t* d_rank, const uint64_t* d_count, uint32_t skip,
                         uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_src_or_null,

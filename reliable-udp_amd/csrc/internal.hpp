@@ -306,6 +306,28 @@ struct WindowArgs {
   uint64_t chunk, chunks;       // this launch's chunk of 1024 new frames, and how many there are (set by the launcher)
 };
 
+// One batch judged for many peers (flows.hip).
+struct FlowsArgs {
+  const uint16_t* seq;
+  const uint8_t* flags;
+  const uint32_t* chars;
+  const uint8_t* usable;        // [n], or null: every frame usable
+  const uint32_t* flow;         // [n]: the slot of each datagram's peer, or RUDP_FLOW_NONE
+  uint64_t n;                   // at most RUDP_FLOWS_MAX_BATCH
+  uint64_t* states;             // [n_flows][4], in place
+  uint64_t n_flows;
+  uint8_t* accept;
+  uint8_t* keep;
+  uint8_t* reply;
+  uint16_t* reply_ack;
+  uint32_t* rank;
+  uint32_t* order;              // [n]
+  uint32_t* order_off;          // [n + 1]; [0..A] written
+  uint64_t* flow_info;          // [n][8]; A rows written
+  uint64_t* info;               // [8]
+  uint32_t* status;
+};
+
 // Payloads out in rank order (ordered.hip).
 struct OrderedArgs {
   const unsigned char* frames;  // moved back to a 16-B boundary by the C entry point
@@ -795,6 +817,8 @@ int launch_accept_inorder(AcceptArgs args, hipStream_t stream);
 // stream's scratch (inside a ScratchCall), and a clearing pass when there is
 // more than one chunk.
 int launch_accept_window(WindowArgs args, hipStream_t stream);
+// Many peers in one batch (flows.hip): one launch of one workgroup, no scratch.
+int launch_accept_flows(const FlowsArgs& args, hipStream_t stream);
 // Payloads in rank order (ordered.hip): five launches, the tile sums and (without
 // the caller's d_src) the source table in the stream's scratch (inside a ScratchCall).
 int launch_gather_ordered(OrderedArgs args, hipStream_t stream);

@@ -31,6 +31,9 @@ ST_LEN, ST_PAYLOAD, ST_FRAMES_CAP, ST_OFFSETS, ST_PAYLOAD_CAP = 1, 2, 4, 8, 16
 ST_PACKETS_CAP = 32  # rudp_segment_utf8: more packets than the tables hold
 ST_RANK = 64  # rudp_gather_ordered: a rank at or above the count that is not RANK_NONE
 ST_CARRY_CAP = 128  # rudp_receive_window: the pending frames need more than carry_cap bytes
+ST_FLOW = 256  # rudp_accept_flows: a d_flow[i] at or above n_flows that is not FLOW_NONE
+FLOW_NONE = 0xFFFFFFFF  # RUDP_FLOW_NONE: a datagram without a flow
+FLOWS_MAX_BATCH = 1024  # RUDP_FLOWS_MAX_BATCH
 RANK_NONE = 0xFFFFFFFF  # RUDP_RANK_NONE
 DUP_BAD_OFFSETS = 2  # rudp_dedup_window_checked: a frame whose offsets were rejected
 
@@ -47,7 +50,7 @@ EXPORTS = (
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
     "rudp_gather_payloads", "rudp_segment_utf8", "rudp_payload_chars", "rudp_accept_inorder",
     "rudp_receive", "rudp_ack_progress", "rudp_acknowledge", "rudp_accept_window", "rudp_gather_ordered",
-    "rudp_receive_window",
+    "rudp_receive_window", "rudp_accept_flows",
 )
 ACK_EXACT, ACK_CUMULATIVE = 0, 1  # RUDP_ACK_*: the mode of rudp_ack_progress / rudp_acknowledge
 
@@ -137,6 +140,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rudp_receive": [P, U64, P, U32, U64, P, U32, P, ctypes.POINTER(RudpReceived), I, I, P],
         "rudp_accept_window": [P, P, P, P, U64, U32, U32, U64, P, P, P, P, P, P, P, P, I, P],
         "rudp_gather_ordered": [P, U64, P, U32, U64, P, P, U32, P, U64, P, P, P, I, P],
+        "rudp_accept_flows": [P, P, P, P, P, U64, P, U64, P, P, P, P, P, P, P, P, P, P, I, P],
         "rudp_receive_window": [P, U64, P, P, U64, P, U64, P, P, U64, U32, U32, U32, P,
                                 ctypes.POINTER(RudpReceivedWindow), I, I, P],
         "rudp_ack_progress": [P, P, P, P, U64, U32, U64, U32, I, U64, P, P, P, P, P, I, P],

@@ -109,6 +109,7 @@ _ST_MESSAGES = (
     (_native.ST_OFFSETS, "frame_off must be non-decreasing offsets inside frames"),
     (_native.ST_PAYLOAD_CAP, "out is too small for the kept payloads"),
     (_native.ST_PACKETS_CAP, "the message makes more packets than max_packets"),
+    (_native.ST_FLOW, "a flow slot is neither below the states table's rows nor FLOW_NONE"),
 )
 
 
@@ -1646,6 +1647,269 @@ def gather_ordered(frames, frame_off, rank, count, *, skip: int, out=None, strea
             base + 8 * (n + 1) + 4 * n, dev.index or 0, _stream_ptr(stream, dev)))
     return OrderedPayloads(buffer, buf[:8 * (n + 1)].view(torch.int64), buf[8 * (n + 1):8 * (n + 1) + 4 * n].view(
         torch.int32), count, buf[8 * (n + 1) + 4 * n:].view(torch.int32))
+
+
+# ------------------------------------------------------------ many peers in one batch
+FLOW_NONE = _native.FLOW_NONE             # a datagram without a flow (-1 in the int32 ``flow`` tensor)
+FLOWS_MAX_BATCH = _native.FLOWS_MAX_BATCH   # datagrams per accept_flows call: one recvmmsg batch
+
+
+def flow_states(n_flows: int, device):
+    """The zero table of ``n_flows`` fresh flows for ``accept_flows``: int64
+    [n_flows, 4] on ``device``, a row {expect, isn, live, last_isn + 1}."""
+    import torch
+    if isinstance(n_flows, bool) or not isinstance(n_flows, int) or not 1 <= n_flows <= 0xFFFFFFFE:
+        raise ValueError(f"n_flows must be an int in [1, 2^32 - 2], got {n_flows!r}")
+    return torch.zeros((n_flows, 4), dtype=torch.int64, device=device)
+
+
+class FlowsAccepted:
+    """Result of ``accept_flows``: one device buffer with cut views.
+    ``accept``, ``keep``, ``reply`` (u8 [N]), ``reply_ack`` (u16 [N]), ``rank``
+    (int32 [N] holding u32 values; -1 is RUDP_RANK_NONE), ``order`` (int32
+    [N]), ``order_off`` (int32 [N + 1], of which [0..A] are written),
+    ``flow_info`` (int64 [N, 8], A rows written), ``info`` (int64 [8]: A, K, R,
+    ended flows, datagrams without a flow, flows walked, 0, 0), ``status``
+    (int32 [1]) and ``states`` (the caller's table, updated in place) as
+    rudp_accept_flows defines them.  ``active``, ``kept``, ``replies``,
+    ``ended``, ``flowless`` and ``flows()`` are read from the device on first
+    use, one synchronization for all; ``check()`` reads the status; nothing
+    else waits."""
+
+    __slots__ = ("_buf", "_n", "_lay", "_views", "_host", "states")
+
+    def __init__(self, buf, n: int, states):
+        self._buf, self._n, self._lay, self.states = buf, n, FlowsAccepted.layout(n), states
+        self._views, self._host = {}, None
+
+    @staticmethod
+    def layout(n: int):
+        """Byte offsets in the one allocation: rank | order (u32 [n]) | order_off
+        (u32 [n + 1]) | reply_ack (u16 [n]) | accept | keep | reply (u8 [n]) |
+        flow_info (u64 [n][8]) | info (u64 [8]) | status (u32); then the size."""
+        lay, at = {}, 0
+        for name, nbytes in (("rank", 4 * n), ("order", 4 * n), ("order_off", 4 * (n + 1)), ("reply_ack", 2 * n),
+                             ("accept", n), ("keep", n), ("reply", n)):
+            lay[name] = at
+            at += nbytes
+        lay["flow_info"] = (at + 7) & ~7
+        lay["info"] = lay["flow_info"] + 64 * n
+        lay["status"] = lay["info"] + 64
+        lay["size"] = lay["status"] + 8
+        return lay
+
+    def _cut(self, name, nbytes, dtype):
+        v = self._views.get(name)
+        if v is None:
+            lo = self._lay[name]
+            v = self._buf[lo:lo + nbytes]
+            v = self._views[name] = v if dtype is None else v.view(dtype)
+        return v
+
+    accept = property(lambda self: self._cut("accept", self._n, None))
+    keep = property(lambda self: self._cut("keep", self._n, None))
+    reply = property(lambda self: self._cut("reply", self._n, None))
+
+    @property
+    def reply_ack(self):
+        import torch
+        return self._cut("reply_ack", 2 * self._n, torch.uint16)
+
+    @property
+    def rank(self):
+        import torch
+        return self._cut("rank", 4 * self._n, torch.int32)
+
+    @property
+    def order(self):
+        import torch
+        return self._cut("order", 4 * self._n, torch.int32)
+
+    @property
+    def order_off(self):
+        import torch
+        return self._cut("order_off", 4 * (self._n + 1), torch.int32)
+
+    @property
+    def flow_info(self):
+        import torch
+        return self._cut("flow_info", 64 * self._n, torch.int64).view(self._n, 8)
+
+    @property
+    def info(self):
+        import torch
+        return self._cut("info", 64, torch.int64)
+
+    @property
+    def status(self):
+        import torch
+        return self._cut("status", 4, torch.int32)
+
+    def _read(self):
+        if self._host is None:
+            import torch
+            lo = self._lay["flow_info"]  # flow_info | info: one copy
+            words = self._buf[lo:self._lay["status"]].view(torch.int64).cpu().numpy()
+            info = [int(v) for v in words[8 * self._n:]]
+            self._host = (info, words[:8 * info[0]].reshape(info[0], 8).copy())
+        return self._host
+
+    active = property(lambda self: self._read()[0][0])
+    kept = property(lambda self: self._read()[0][1])
+    replies = property(lambda self: self._read()[0][2])
+    ended = property(lambda self: self._read()[0][3])
+    flowless = property(lambda self: self._read()[0][4])
+
+    def flows(self):
+        """int64 [A, 8] on the host, ascending by slot: slot, end, accepted,
+        msg_start, characters, isn, kept, rank base of every active flow."""
+        return self._read()[1]
+
+    def check(self) -> "FlowsAccepted":
+        _raise_status(self.status)
+        return self
+
+    def __len__(self) -> int:
+        return self._n
+
+
+def _flows_tensor(t, name, dev, dtypes, n=None, ndim=1):
+    if not _is_torch(t):
+        raise TypeError(f"{name} must be a torch tensor on a HIP device (no host-memory form)")
+    if t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, expected {dev}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{name} must be {'/'.join(map(str, dtypes))}, got {t.dtype}")
+    if t.dim() != ndim or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {ndim}-D tensor, got shape {tuple(t.shape)}")
+    if n is not None and t.shape[0] != n:
+        raise ValueError(f"{name} has {t.shape[0]} entries, expected {n}")
+
+
+def accept_flows(seq, flags, chars, flow, *, states, usable=None, stream=None) -> FlowsAccepted:
+    """``accept_inorder`` for a batch that carries datagrams of many peers
+    (rudp_accept_flows; include/rudp.h states the rule): ``flow`` (int32 [N]
+    holding u32 values) names each datagram's row in ``states`` (int64
+    [n_flows, 4] from ``flow_states``, updated in place), -1 (``FLOW_NONE``) a
+    datagram to ignore.  Every flow is judged by the in-order rule on its own
+    datagrams in arrival order, all flows in one launch; a flow whose transfer
+    ends turns over to a closed row.  ``seq``, ``flags``, ``chars`` and
+    ``usable`` as ``accept_inorder`` takes them; at most ``FLOWS_MAX_BATCH``
+    datagrams.  Never waits; ``check()`` on the result raises when a slot was
+    out of range."""
+    for name, t in (("seq", seq), ("flags", flags), ("chars", chars), ("flow", flow), ("states", states)):
+        if not _is_torch(t):
+            raise TypeError(f"accept_flows takes torch tensors on a HIP device (no host-memory form): {name}")
+    import torch
+    dev = seq.device
+    if dev.type != "cuda":
+        raise ValueError("accept_flows runs on a HIP device")
+    _flows_tensor(seq, "seq", dev, (torch.uint16,))
+    n = seq.shape[0]
+    if n > FLOWS_MAX_BATCH:
+        raise ValueError(f"accept_flows takes at most {FLOWS_MAX_BATCH} datagrams (one recvmmsg batch), got {n}")
+    _flows_tensor(flags, "flags", dev, (torch.uint8,), n)
+    _flows_tensor(chars, "chars", dev, (torch.int32,), n)
+    _flows_tensor(flow, "flow", dev, (torch.int32,), n)
+    if usable is not None:
+        _flows_tensor(usable, "usable", dev, (torch.uint8, torch.bool), n)
+    _flows_tensor(states, "states", dev, (torch.int64,), ndim=2)
+    if states.shape[1] != 4 or not 1 <= states.shape[0] <= 0xFFFFFFFE:
+        raise ValueError(f"states must be int64 [n_flows, 4] with 1 <= n_flows <= 2^32 - 2, got {tuple(states.shape)}")
+    lay = FlowsAccepted.layout(n)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        buf = torch.empty(lay["size"], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+
+    def tab(t):
+        return t if n else None
+
+    _native.check(_native.lib().rudp_accept_flows(
+        tab(seq.data_ptr()), tab(flags.data_ptr()), tab(chars.data_ptr()),
+        usable.data_ptr() if usable is not None and n else None, tab(flow.data_ptr()), n, states.data_ptr(),
+        states.shape[0], tab(base + lay["accept"]), tab(base + lay["keep"]), tab(base + lay["reply"]),
+        tab(base + lay["reply_ack"]), tab(base + lay["rank"]), tab(base + lay["order"]), tab(base + lay["order_off"]),
+        tab(base + lay["flow_info"]), base + lay["info"], base + lay["status"], dev.index or 0,
+        _stream_ptr(stream, dev)))
+    return FlowsAccepted(buf, n, states)
+
+
+class ReceivedFlows:
+    """Result of ``receive_flows``.  ``decoded`` (``VarlenDecoded``: seq, ack,
+    flags, ok, valid), ``usable`` (u8 [N]), ``chars`` (int32 [N]), ``accepted``
+    (``FlowsAccepted``) and ``pieces`` (``OrderedPayloads``: every active flow's
+    part of its message, back to back in flow order).  ``message(a)`` is the
+    piece of active flow a (row a of ``accepted.flows()``), as bytes;
+    ``reply_index`` (int64 [R]: the datagram each reply answers, and whose
+    source it goes to), ``reply_ack`` (u16 [R]) and ``reply_frames(layout)``
+    as ``ReceivedWindow`` has them.  The host reads wait once each, on first
+    use."""
+
+    __slots__ = ("decoded", "usable", "chars", "accepted", "pieces", "_bytes", "_reply")
+
+    def __init__(self, decoded, usable, chars, accepted, pieces):
+        self.decoded, self.usable, self.chars, self.accepted, self.pieces = decoded, usable, chars, accepted, pieces
+        self._bytes, self._reply = None, None
+
+    def message(self, a: int) -> bytes:
+        rows = self.accepted.flows()
+        if self._bytes is None:
+            K = self.accepted.kept
+            off = self.pieces.out_off[:K + 1].cpu().numpy()
+            self._bytes = (off, self.pieces.buffer[:int(off[K])].cpu().numpy().tobytes() if K else b"")
+        off, data = self._bytes
+        base, kept = int(rows[a][7]), int(rows[a][6])
+        return data[int(off[base]):int(off[base + kept])] if kept else b""
+
+    def _replies(self):
+        if self._reply is None:
+            import torch
+            idx = torch.nonzero(self.accepted.reply).flatten()
+            self._reply = (idx, self.accepted.reply_ack.view(torch.int16)[idx].view(torch.uint16))
+        return self._reply
+
+    reply_index = property(lambda self: self._replies()[0])
+    reply_ack = property(lambda self: self._replies()[1])
+    reply_count = property(lambda self: int(self._replies()[0].shape[0]))
+
+    def reply_frames(self, layout: Union[str, int] = "rudp7"):
+        """u8 [R * H]: the reply datagrams, header-only frames at stride H in
+        arrival order (seq 0, ack = reply_ack, flags ACK)."""
+        import torch
+        ack = self.reply_ack
+        R = ack.shape[0]
+        empty = torch.empty(0, dtype=torch.uint8, device=ack.device)
+        if R == 0:
+            return empty
+        tab = (torch.zeros_like(ack), ack, torch.full((R,), ACK, dtype=torch.uint8, device=ack.device))
+        return pack_batch_varlen(tab, empty, torch.zeros(R, dtype=torch.int32, device=ack.device), layout,
+                                 want_csum=False, check=False).frames
+
+
+def receive_flows(frames, frame_off, flow, layout: Union[str, int] = "rudp7", *, states, csum=None,
+                  stream=None) -> ReceivedFlows:
+    """``receive_batch`` for a batch that carries datagrams of many peers, with
+    no host wait in between: ``unpack_batch_varlen(utf8=True)`` -> ``keep_mask``
+    -> ``payload_chars`` -> ``accept_flows`` -> ``gather_ordered`` (rank, K,
+    skip = the header), which leaves every active flow's message piece back to
+    back.  ``flow`` and ``states`` as ``accept_flows`` takes them; ``csum``:
+    the rudp5 sideband."""
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off) or not _is_torch(flow):
+        raise TypeError("receive_flows takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    if frame_off.dim() != 1 or frame_off.shape[0] < 1:
+        raise ValueError("frame_off needs N + 1 entries")
+    if frame_off.shape[0] - 1 > FLOWS_MAX_BATCH:
+        raise ValueError(f"receive_flows takes at most {FLOWS_MAX_BATCH} datagrams (one recvmmsg batch), "
+                         f"got {frame_off.shape[0] - 1}")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        dec = unpack_batch_varlen(frames, frame_off, H, csum=csum, check=False, utf8=True)
+        usable = keep_mask(dec, unverified=H == 5 and csum is None)
+        chars = payload_chars(frames, frame_off, H)
+        acc = accept_flows(dec.seq, dec.flags, chars, flow, states=states, usable=usable)
+        pieces = gather_ordered(frames, frame_off, acc.rank, acc.info[1:2], skip=H)
+    return ReceivedFlows(dec, usable, chars, acc, pieces)
 
 
 class CarriedFrames:

@@ -1,0 +1,202 @@
+"""Many peers on one socket: the host side of ``batch.receive_flows``.
+
+``FlowTable`` maps a datagram's source (``netio.addr_key``) to the slot of its
+peer's row in the device state table.  ``FlowReceiver`` is the small server
+built on it: every recvmmsg batch, whatever mix of concurrent transfers it
+carries, is judged on the device in one ``receive_flows`` call, the replies go
+out with one sendmmsg, each to its own datagram's source, and every transfer
+that ends is returned as ``(addr, text)`` and closed with the reference's
+FIN|ACK handshake (``ReliableUDP._finish_recv``), kept per peer so that one
+peer's lost FIN|ACK never holds up another peer's transfer.
+"""
+from __future__ import annotations
+
+import time
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+from . import _native
+from .batch import ACK, FIN, SYN, flow_states, layout_header_len
+from .transport import FIN_WAIT_S, MAX_DATAGRAM, MAX_SENDS, build
+
+FLOW_NONE = _native.FLOW_NONE
+
+
+class FlowTable:
+    """``addr_key`` -> slot, on the host.  A new peer gets the lowest free slot;
+    with the table full an unknown peer gets ``FLOW_NONE`` (its datagrams are
+    ignored) until a slot is released."""
+
+    def __init__(self, capacity: int):
+        if isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity <= 0xFFFFFFFE:
+            raise ValueError(f"capacity must be an int in [1, 2^32 - 2], got {capacity!r}")
+        self.capacity = capacity
+        self._slot: Dict[int, int] = {}
+        self._key: Dict[int, int] = {}
+        self._next = 0               # slots at or above it were never handed out
+        self._freed: List[int] = []  # released slots, kept sorted descending (pop gives the lowest)
+        self.allocations = 0         # slots ever handed out
+
+    def __len__(self) -> int:
+        return len(self._slot)
+
+    def slot_of(self, key: int) -> Optional[int]:
+        return self._slot.get(int(key))
+
+    def key_of(self, slot: int) -> Optional[int]:
+        return self._key.get(int(slot))
+
+    def _allocate(self, key: int) -> int:
+        if self._freed:
+            slot = self._freed.pop()
+        elif self._next < self.capacity:
+            slot, self._next = self._next, self._next + 1
+        else:
+            return FLOW_NONE
+        self._slot[key], self._key[slot] = slot, key
+        self.allocations += 1
+        return slot
+
+    def slots(self, sources) -> np.ndarray:
+        """u32 [n]: the slot of every datagram's source, new peers allocated.
+        One ``np.unique`` over the batch and one lookup per distinct peer."""
+        keys, inverse = np.unique(np.asarray(sources, dtype=np.uint64), return_inverse=True)
+        per = np.empty(keys.shape[0], np.uint32)
+        for j, key in enumerate(keys.tolist()):
+            slot = self._slot.get(key)
+            per[j] = self._allocate(key) if slot is None else slot
+        return per[inverse.reshape(-1)]
+
+    def release(self, slot: int) -> None:
+        key = self._key.pop(int(slot), None)
+        if key is None:
+            return
+        del self._slot[key]
+        self._freed.append(int(slot))
+        self._freed.sort(reverse=True)
+
+
+class _Closing:
+    """A finished transfer whose FIN|ACK waits for the peer's final ACK."""
+    __slots__ = ("frame", "isn", "sends_left", "deadline", "after")
+
+    def __init__(self, frame: bytes, isn: int, deadline: float, after: int):
+        self.frame, self.isn, self.sends_left, self.deadline, self.after = frame, isn, MAX_SENDS - 1, deadline, after
+
+
+class FlowReceiver:
+    """A multi-peer receiver on one bound UDP socket.
+
+        rx = FlowReceiver(sock, "cuda:0")
+        for addr, text in rx.serve(3): ...
+
+    ``poll(timeout_ms)`` takes one recvmmsg batch (one wait for the device per
+    batch) and returns the transfers it completed; ``serve(count)`` polls until
+    ``count`` messages are in.  ``table`` (``FlowTable``) and ``states`` (the
+    device table) are the per-peer state; ``closing`` the slots whose FIN|ACK
+    still waits for the final ACK."""
+
+    def __init__(self, sock, device, max_flows: int = 1024, layout="rudp5"):
+        import torch
+        from . import netio
+        self.sock, self.layout, self.H = sock, layout, layout_header_len(layout)
+        self.device = torch.device(device)
+        self.table = FlowTable(max_flows)
+        self.states = flow_states(max_flows, self.device)
+        self.rx = netio.BatchReceiver(sock, max_msgs=_native.FLOWS_MAX_BATCH, slot_bytes=MAX_DATAGRAM, slots=2,
+                                      device=self.device, with_sources=True)
+        self.closing: Dict[int, _Closing] = {}
+        self._parts: Dict[int, List[bytes]] = {}
+
+    def _send_to(self, frame: bytes, key: int) -> None:
+        from . import netio
+        self.sock.sendto(frame, netio.key_addr(key))
+
+    def _release(self, slot: int) -> None:
+        self.closing.pop(slot, None)
+        self._parts.pop(slot, None)
+        self.table.release(slot)
+        self.states[slot].zero_()  # a fresh flow for the slot's next peer (ordered before the next batch's call)
+
+    def _resend(self, slot: int, c: _Closing, now: float) -> None:
+        if c.sends_left > 0:
+            self._send_to(c.frame, self.table.key_of(slot))
+            c.sends_left -= 1
+            c.deadline = now + FIN_WAIT_S
+        else:
+            self._release(slot)
+
+    def poll(self, timeout_ms: int = -1) -> List[Tuple[Tuple[str, int], str]]:
+        from . import netio
+        import torch
+        wait = timeout_ms
+        if self.closing:
+            due = max(0.0, min(c.deadline for c in self.closing.values()) - time.monotonic())
+            due_ms = int(due * 1e3) + 1
+            wait = due_ms if timeout_ms < 0 else min(timeout_ms, due_ms)
+        self.sock.setblocking(True)
+        n = self.rx.recv(timeout_ms=wait)
+        done: List[Tuple[Tuple[str, int], str]] = []
+        if n:
+            sources = self.rx.sources.copy()
+            slots = self.table.slots(sources)
+            res, _, _ = self.rx.receive_flows(slots, self.layout, states=self.states)
+            rows = res.accepted.flows()  # (the one wait per batch; every host read below is behind it)
+            idx = res.reply_index.cpu().numpy()
+            if idx.shape[0]:
+                netio.send_batch_to(self.sock, res.reply_frames(self.layout).cpu().numpy(),
+                                    self.H * np.arange(idx.shape[0] + 1, dtype=np.int64), sources[idx])
+            now = time.monotonic()
+            for a in range(rows.shape[0]):
+                slot, end, _, msg_start, characters, isn, kept, _ = (int(v) for v in rows[a])
+                if msg_start < n:  # a new transfer of this peer started in the batch
+                    self._parts[slot] = []
+                    self.closing.pop(slot, None)
+                if kept:
+                    self._parts.setdefault(slot, []).append(res.message(a))
+                if end < n:
+                    text = b"".join(self._parts.pop(slot, [])).decode()
+                    key = self.table.key_of(slot)
+                    done.append((netio.key_addr(key), text))
+                    fin = build(0, isn + characters, FIN | ACK)
+                    self._send_to(fin, key)
+                    self.closing[slot] = _Closing(fin, isn, now + FIN_WAIT_S, end)
+            if self.closing:
+                dec = res.decoded
+                seq = dec.seq.view(torch.int16).cpu().numpy().view(np.uint16)
+                ack = dec.ack.view(torch.int16).cpu().numpy().view(np.uint16)
+                flags = dec.flags.cpu().numpy()
+                usable = res.usable.cpu().numpy() != 0
+                for slot, c in list(self.closing.items()):
+                    mine = np.flatnonzero((slots == slot) & usable)
+                    mine = mine[mine > c.after]
+                    c.after = -1
+                    resend = False
+                    for i in mine.tolist():
+                        f = int(flags[i])
+                        if f & ACK and not f & SYN and int(ack[i]) == 1:  # the handshake is complete
+                            self._release(slot)
+                            resend = False
+                            break
+                        if not f & ACK or (f & SYN and int(seq[i]) == c.isn):
+                            resend = True
+                    if resend:
+                        self._resend(slot, c, now)
+        now = time.monotonic()
+        for slot, c in list(self.closing.items()):
+            if now >= c.deadline:  # FIN_WAIT_S without the final ACK
+                self._resend(slot, c, now)
+        return done
+
+    def serve(self, count: int, timeout: Optional[float] = None) -> List[Tuple[Tuple[str, int], str]]:
+        """Poll until ``count`` messages are complete (or ``timeout`` seconds
+        have passed) and return them as ``(addr, text)`` in completion order."""
+        out: List[Tuple[Tuple[str, int], str]] = []
+        stop = None if timeout is None else time.monotonic() + timeout
+        while len(out) < count:
+            left = -1 if stop is None else int(max(0.0, stop - time.monotonic()) * 1e3)
+            if stop is not None and left == 0:
+                break
+            out.extend(self.poll(left))
+        return out

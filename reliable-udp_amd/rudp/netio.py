@@ -335,6 +335,45 @@ class BatchReceiver:
             t.record_stream(cur)
         return res, d_frames, d_off
 
+    def receive_flows(self, flow, layout="rudp5", *, states, csum=None, stream=None):
+        """H2D of the received frames as ``receive()`` does it (the same slot and
+        event bookkeeping) and of ``flow`` (numpy u32 [count]: each datagram's
+        slot in ``states``, from ``flows.FlowTable.slots(self.sources)``), then
+        ``batch.receive_flows``: the batch judged for all its peers at once.
+        Never waits for the device.
+
+        Returns ``(ReceivedFlows, d_frames, d_frame_off)``; reply k answers
+        datagram ``res.reply_index[k]`` and goes to that datagram's source."""
+        import torch
+        s = stream if stream is not None else self.stream
+        k, n = self._slot, self.count
+        if k < 0:
+            raise RuntimeError("receive_flows() before any recv()")
+        flow = np.ascontiguousarray(flow, dtype=np.uint32)
+        if flow.shape != (n,):
+            raise ValueError(f"flow has shape {flow.shape} for {n} datagrams")
+        total = int(self._off_t[k][n])
+        h_flow = torch.from_numpy(flow.view(np.int32)).pin_memory()
+        s.wait_stream(torch.cuda.current_stream(self.device))  # e.g. csum or states written by the caller
+        with torch.cuda.stream(s):
+            d_frames = torch.empty((total,), dtype=torch.uint8, device=self.device)
+            d_off = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+            d_flow = torch.empty((n,), dtype=torch.int32, device=self.device)
+            d_frames.copy_(self._frames_t[k][:total], non_blocking=True)
+            d_off.copy_(self._off_t[k][:n + 1], non_blocking=True)
+            d_flow.copy_(h_flow, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(s)
+            self._copied[k] = ev
+            res = _batch.receive_flows(d_frames, d_off, d_flow, layout, states=states, csum=csum)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(s)
+        # allocated on `s`, used on the caller's stream from here on
+        for t in (d_frames, d_off, d_flow, res.decoded._buf, res.usable, res.chars, res.accepted._buf,
+                  res.pieces.buffer, res.pieces.out_off):
+            t.record_stream(cur)
+        return res, d_frames, d_off
+
     def acknowledge(self, layout="rudp5", *, isn, total_chars, chunk=1, state=None, mode="exact", sent=None,
                     csum=None, stream=None):
         """H2D of the received reply datagrams as ``receive()`` does it (the same

@@ -822,6 +822,107 @@ RUDP_API int rudp_receive_window(const uint8_t* d_carried, uint64_t carried_byte
                                  const rudp_received_window* out, int layout, int device, void* hip_stream);
 
 /*
+ * The many-peer receiver in one call (added within ABI 8,
+ * RUDP_HAS_RECEIVE_FLOWS): rudp_receive for a server whose recvmmsg batch
+ * carries datagrams of many transfers.  One call does
+ * rudp_decode_varlen_utf8, the usable mask, rudp_payload_chars,
+ * rudp_accept_flows (usable as its mask) and rudp_gather_ordered(rank, K =
+ * info[1], skip = layout), every output bit for bit what those calls write,
+ * and builds the reply datagrams and, for every flow whose transfer ended, the
+ * closing datagram its peer is owed.  Sync-free as rudp_receive: asynchronous
+ * on hip_stream, the host never waits, temporaries come from the stream's
+ * set, usable under stream capture.  A batch in at most 32768 bytes and 133
+ * bytes per datagram is one launch of one workgroup that reads the frames
+ * once; other batches run the launches of the five calls and one finishing
+ * pass.
+ *
+ * Inputs: d_frames, frames_bytes, d_frame_off[n + 1], len_hint, n,
+ * d_csum_in_or_null and layout as rudp_decode_varlen_utf8 takes them; d_flow,
+ * d_states (read and written in place) and n_flows as rudp_accept_flows.  A
+ * frame rejected by the offset rule gets ok = RUDP_OK_BAD_OFFSETS, is
+ * unusable, sets RUDP_ST_OFFSETS and is never ranked.  Outputs through *out
+ * (device pointers; n entries each unless said otherwise):
+ *   seq, ack, flags, ok, csum_out_or_null, valid, usable, chars
+ *                 as rudp_receive defines them
+ *   accept, keep, reply, reply_ack, rank, order, order_off[n + 1],
+ *   flow_info[n][8], info[0..7] and d_states
+ *                 exactly rudp_accept_flows with `usable` as its mask
+ *   payload, payload_cap, payload_off[n + 1], payload_src_or_null[n]
+ *                 every active flow's message piece back to back in flow
+ *                 order: exactly rudp_gather_ordered's; payload_off[0..K] and
+ *                 payload_src[0..K - 1] are written (flow a's piece is
+ *                 payload[payload_off[b], payload_off[b + kept]) with b =
+ *                 flow_info[a][7], kept = flow_info[a][6]).  When the total
+ *                 exceeds payload_cap, RUDP_ST_PAYLOAD_CAP is set, no byte of
+ *                 payload is written and payload_off[K] holds the size needed;
+ *                 nothing is written at or past the total
+ *   reply_frames, reply_csum_or_null, reply_index
+ *                 as rudp_receive: R = info[2] header-only frames of `layout`
+ *                 bytes at stride `layout`, in arrival order (seq 0, ack =
+ *                 reply_ack[i], flags 0x40, the checksum in-band for layout
+ *                 7); reply_index[k] = i.  A reply goes to the source of its
+ *                 own datagram, so there is no reply_peer.  The caller
+ *                 provides n * layout bytes (and n entries of the tables);
+ *                 nothing is written at or past R * layout
+ *   fin_frames, fin_csum_or_null, fin_flow
+ *                 E = info[3] closing datagrams, one for every active flow a
+ *                 with flow_info[a][1] < n, in ascending a: the header-only
+ *                 frame with seq 0, ack = (flow_info[a][5] + flow_info[a][4])
+ *                 mod 2^16 (the ISN plus the characters received) and flags
+ *                 0x60 (FIN|ACK), the checksum in-band for layout 7 and in
+ *                 fin_csum for both layouts; fin_flow[e] = a (u32), the peer
+ *                 being that of slot flow_info[a][0].  The caller provides
+ *                 n * layout bytes and n entries; nothing is written at or
+ *                 past E * layout
+ *   info          u64[12]: [0..7] as rudp_accept_flows' d_info; [8] = the
+ *                 message bytes (payload_off[K]); [9..11] = 0
+ *   status        u32, required, written once: RUDP_ST_OFFSETS | RUDP_ST_FLOW
+ *                 | RUDP_ST_PAYLOAD_CAP, or 0
+ * n == 0 writes info = 0 and status = 0 and touches nothing else, not even
+ * d_states.  n > RUDP_FLOWS_MAX_BATCH returns RUDP_ENOTSUP.  RUDP_EINVAL
+ * before any HIP call: out NULL; a layout other than 5 or 7; a sideband
+ * d_csum_in with layout 7; d_states, info or status NULL; n_flows 0 or above
+ * 2^32 - 2; with n > 0, d_frame_off, d_flow or any table other than the
+ * _or_null ones NULL, d_frames NULL with frames_bytes > 0, or payload NULL
+ * with payload_cap > 0.
+ */
+#define RUDP_HAS_RECEIVE_FLOWS 1
+typedef struct rudp_received_flows {
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint8_t* ok;
+  uint16_t* csum_out_or_null;
+  uint8_t* valid;
+  uint8_t* usable;
+  uint32_t* chars;
+  uint8_t* accept;
+  uint8_t* keep;
+  uint8_t* reply;
+  uint16_t* reply_ack;
+  uint32_t* rank;
+  uint32_t* order;
+  uint32_t* order_off;
+  uint64_t* flow_info;
+  uint8_t* payload;
+  uint64_t payload_cap;
+  uint64_t* payload_off;
+  uint32_t* payload_src_or_null;
+  uint8_t* reply_frames;
+  uint16_t* reply_csum_or_null;
+  uint32_t* reply_index;
+  uint8_t* fin_frames;
+  uint16_t* fin_csum_or_null;
+  uint32_t* fin_flow;
+  uint64_t* info;
+  uint32_t* status;
+} rudp_received_flows;
+RUDP_API int rudp_receive_flows(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off,
+                                uint32_t len_hint, uint64_t n, const uint16_t* d_csum_in_or_null,
+                                const uint32_t* d_flow, uint64_t* d_states, uint64_t n_flows,
+                                const rudp_received_flows* out, int layout, int device, void* hip_stream);
+
+/*
  * The sender's judgement of a reply batch (added within ABI 8,
  * RUDP_HAS_ACKNOWLEDGE): wait_ack of utils/reliableUDP.py:64-85 for every
  * reply datagram of one recvmmsg, and the closing packet of send_ack (:87-93).

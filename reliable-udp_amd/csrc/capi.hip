@@ -1540,6 +1540,114 @@ int rudp_receive_window(const uint8_t* d_carried, uint64_t carried_bytes, const 
   return 0;
 }
 
+int rudp_receive_flows(const uint8_t* d_frames, uint64_t frames_bytes, const uint64_t* d_frame_off, uint32_t len_hint,
+                       uint64_t n, const uint16_t* d_csum_in_or_null, const uint32_t* d_flow, uint64_t* d_states,
+                       uint64_t n_flows, const rudp_received_flows* out, int layout, int device, void* hip_stream) {
+  if (!out) return fail(RUDP_EINVAL, "rudp_receive_flows: out is NULL");
+  if (layout != RUDP_LAYOUT_RUDP5 && layout != RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "unsupported layout %d (use 5 or 7)", layout);
+  if (d_csum_in_or_null && layout == RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "rudp_receive_flows: d_csum_in with layout 7 (its checksum is in-band)");
+  if (!d_states) return fail(RUDP_EINVAL, "rudp_receive_flows: d_states is NULL");
+  if (!out->info) return fail(RUDP_EINVAL, "rudp_receive_flows: info is NULL");
+  if (!out->status) return fail(RUDP_EINVAL, "rudp_receive_flows: status is NULL");
+  if (n_flows < 1u || n_flows > 0xFFFFFFFEull)
+    return fail(RUDP_EINVAL, "rudp_receive_flows: n_flows %llu outside [1, 2^32 - 2]", (unsigned long long)n_flows);
+  if (n > RUDP_FLOWS_MAX_BATCH)
+    return fail(RUDP_ENOTSUP, "rudp_receive_flows: n %llu exceeds RUDP_FLOWS_MAX_BATCH (%u datagrams, one recvmmsg batch)",
+                (unsigned long long)n, RUDP_FLOWS_MAX_BATCH);
+  if (n) {
+    if (!d_frame_off) return fail(RUDP_EINVAL, "rudp_receive_flows: d_frame_off is NULL");
+    if (!d_flow) return fail(RUDP_EINVAL, "rudp_receive_flows: d_flow is NULL");
+    if (!d_frames && frames_bytes) return fail(RUDP_EINVAL, "rudp_receive_flows: d_frames is NULL");
+    const struct {
+      const void* p;
+      const char* name;
+    } tables[] = {{out->seq, "seq"}, {out->ack, "ack"}, {out->flags, "flags"}, {out->ok, "ok"},
+                  {out->valid, "valid"}, {out->usable, "usable"}, {out->chars, "chars"}, {out->accept, "accept"},
+                  {out->keep, "keep"}, {out->reply, "reply"}, {out->reply_ack, "reply_ack"}, {out->rank, "rank"},
+                  {out->order, "order"}, {out->order_off, "order_off"}, {out->flow_info, "flow_info"},
+                  {out->payload_off, "payload_off"}, {out->reply_frames, "reply_frames"},
+                  {out->reply_index, "reply_index"}, {out->fin_frames, "fin_frames"}, {out->fin_flow, "fin_flow"}};
+    for (const auto& t : tables)
+      if (!t.p) return fail(RUDP_EINVAL, "rudp_receive_flows: %s is NULL", t.name);
+    if (!out->payload && out->payload_cap) return fail(RUDP_EINVAL, "rudp_receive_flows: payload is NULL");
+  }
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  RecvFlowsArgs a{};
+  // the frames pointer moved back to a 16-B boundary: every load is an aligned block
+  a.fmis = reinterpret_cast<uintptr_t>(d_frames) & 15u;
+  a.frames = d_frames - a.fmis;
+  a.frames_bytes = frames_bytes;
+  a.frame_off = d_frame_off;
+  a.csum_in = d_csum_in_or_null;
+  a.H = (uint32_t)layout;
+  a.f.seq = a.seq = out->seq;
+  a.f.flags = a.flags = out->flags;
+  a.f.chars = a.chars = out->chars;
+  a.f.usable = a.usable = out->usable;
+  a.f.flow = d_flow;
+  a.f.n = n;
+  a.f.states = d_states;
+  a.f.n_flows = n_flows;
+  a.f.accept = out->accept;
+  a.f.keep = out->keep;
+  a.f.reply = out->reply;
+  a.f.reply_ack = out->reply_ack;
+  a.f.rank = out->rank;
+  a.f.order = out->order;
+  a.f.order_off = out->order_off;
+  a.f.flow_info = out->flow_info;
+  a.f.info = a.info = out->info;
+  a.ack = out->ack;
+  a.ok = out->ok;
+  a.csum_out = out->csum_out_or_null;
+  a.valid = out->valid;
+  a.payload = out->payload;
+  a.payload_cap = out->payload_cap;
+  a.payload_off = out->payload_off;
+  a.payload_src = out->payload_src_or_null;
+  a.reply_frames = out->reply_frames;
+  a.reply_csum = out->reply_csum_or_null;
+  a.reply_index = out->reply_index;
+  a.fin_frames = out->fin_frames;
+  a.fin_csum = out->fin_csum_or_null;
+  a.fin_flow = out->fin_flow;
+  a.status = out->status;
+  if (receive_flows_fused_ok(n, frames_bytes)) {
+    rc = launch_receive_flows_fused(a, s);
+    if (rc) return hip_fail((hipError_t)rc, "fused flows receive launch");
+    return 0;
+  }
+  // The chained form: the five calls' launches back to back on the stream,
+  // their temporaries from one set, each with a status word of its own, and
+  // the pass that builds the datagrams and writes the caller's status once.
+  ScratchCall call(s);
+  uint32_t* words = nullptr;
+  RUDP_HIP(stream_scratch(reinterpret_cast<void**>(&words), 4u * sizeof(uint32_t), s, kScratchHash));
+  a.words = words;
+  rc = rudp_decode_varlen_utf8(d_frames, frames_bytes, d_frame_off, len_hint, n, d_csum_in_or_null, a.seq, a.ack,
+                               a.flags, a.ok, a.csum_out, a.valid, words, layout, device, hip_stream);
+  if (rc) return rc;
+  rc = launch_receive_usable(a.ok, a.valid, a.usable, n, s);
+  if (rc) return hip_fail((hipError_t)rc, "usable mask launch");
+  rc = rudp_payload_chars(d_frames, frames_bytes, d_frame_off, len_hint, n, a.chars, layout, device, hip_stream);
+  if (rc) return rc;
+  rc = rudp_accept_flows(a.seq, a.flags, a.chars, a.usable, d_flow, n, d_states, n_flows, out->accept, out->keep,
+                         out->reply, out->reply_ack, out->rank, out->order, out->order_off, out->flow_info, a.info,
+                         words + 1, device, hip_stream);
+  if (rc) return rc;
+  rc = rudp_gather_ordered(d_frames, frames_bytes, d_frame_off, len_hint, n, out->rank, a.info + 1, (uint32_t)layout,
+                           a.payload, a.payload_cap, a.payload_off, a.payload_src, words + 2, device, hip_stream);
+  if (rc) return rc;
+  rc = launch_receive_flows_finish(a, s);
+  if (rc) return hip_fail((hipError_t)rc, "flows receive finish launch");
+  return 0;
+}
+
 // The scalar arguments the two acknowledge entries share.
 static int ack_check_scalars(const char* who, uint32_t isn, uint64_t total_chars, uint32_t chunk_chars, int mode,
                              uint64_t sent_chars) {

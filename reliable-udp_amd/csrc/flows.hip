@@ -26,7 +26,10 @@
 //   6. keep, and an exclusive count of the kept datagrams in sorted order: the
 //      ranks of the flow-major message order, K, R, every run's rank base;
 //   7. the rows and d_flow_info.
-// The device function is in flows_device.hpp.
+// The device functions are in flows_device.hpp: flows_judge is step 1
+// (flows_reset, flows_load) and flows_judge_lds, steps 2 to 7 on the LDS
+// tables, which the fused rudp_receive_flows (receive_flows.hip) enters with
+// tables it filled itself.
 #include "flows_device.hpp"
 
 namespace RUDP_NS {

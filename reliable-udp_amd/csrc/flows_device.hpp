@@ -81,39 +81,49 @@ __device__ inline FlowP flow_block_exclusive_join(FlowP x, FlowLds& L) {
   return flow_join(before, ex);
 }
 
-// The whole call for one workgroup of kBlock threads (0 <= n <= kFlowMax).
-__device__ inline void flows_judge(const FlowsArgs& a, FlowLds& L) {
-  const uint32_t tid = threadIdx.x, n = (uint32_t)a.n;
-  if (n == 0) {  // (uniform)
-    if (tid < 8) a.info[tid] = 0;
-    if (tid == 0) *a.status = 0;
-    return;
-  }
+// Step 1 is split off from the rest, so that a caller whose tables are already
+// in registers (the fused rudp_receive_flows: receive_flows.hip) fills the LDS
+// tables itself: flows_reset (a barrier follows, before the first flows_put;
+// it returns the padded batch size of the sort), flows_put / flows_pad per
+// datagram, and flows_load, the loop over global memory.
+__device__ __forceinline__ uint32_t flows_reset(FlowLds& L, uint32_t n) {
   uint32_t N2 = 2;
   while (N2 < n) N2 <<= 1;
-  if (tid == 0) {
+  if (threadIdx.x == 0) {
     L.bad = 0;
     L.ended = 0;
     L.walked = 0;
   }
-  __syncthreads();
+  return N2;
+}
 
-  // 1. the tables and the keys
-  for (uint32_t k = tid; k < N2; k += kBlock) {
-    uint64_t key = ~0ull;
-    if (k < n) {
-      const uint32_t f = a.flow[k];
-      const bool valid = (uint64_t)f < a.n_flows;  // (n_flows <= 2^32 - 2: RUDP_FLOW_NONE never is)
-      if (!valid && f != RUDP_FLOW_NONE) L.bad = 1;
-      L.seq[k] = a.seq[k];
-      L.fl[k] = a.flags[k];
-      L.ch[k] = a.chars[k];
-      L.us[k] = (uint8_t)(valid && (a.usable ? a.usable[k] != 0 : true));
-      key = (uint64_t)(valid ? f : RUDP_FLOW_NONE) << 10 | k;
-    }
-    L.key[k] = key;
+// 1. datagram k's entries of the tables and its key (k < n), or the padding key
+__device__ __forceinline__ void flows_put(const FlowsArgs& a, FlowLds& L, uint32_t k, uint32_t seq, uint32_t fl,
+                                          uint32_t ch, bool usable) {
+  const uint32_t f = a.flow[k];
+  const bool valid = (uint64_t)f < a.n_flows;  // (n_flows <= 2^32 - 2: RUDP_FLOW_NONE never is)
+  if (!valid && f != RUDP_FLOW_NONE) L.bad = 1;
+  L.seq[k] = (uint16_t)seq;
+  L.fl[k] = (uint8_t)fl;
+  L.ch[k] = ch;
+  L.us[k] = (uint8_t)(valid && usable);
+  L.key[k] = (uint64_t)(valid ? f : RUDP_FLOW_NONE) << 10 | k;
+}
+__device__ __forceinline__ void flows_pad(FlowLds& L, uint32_t k) { L.key[k] = ~0ull; }
+
+// 1. the tables and the keys from global memory
+__device__ __forceinline__ void flows_load(const FlowsArgs& a, FlowLds& L, uint32_t N2) {
+  const uint32_t n = (uint32_t)a.n;
+  for (uint32_t k = threadIdx.x; k < N2; k += kBlock) {
+    if (k < n) flows_put(a, L, k, a.seq[k], a.flags[k], a.chars[k], a.usable ? a.usable[k] != 0 : true);
+    else flows_pad(L, k);
   }
-  __syncthreads();
+}
+
+// Steps 2 to 7 on the tables and keys of step 1 (behind a barrier; 1 <= n <=
+// kFlowMax, N2 from flows_reset).  status, when not null, gets the call's word.
+__device__ inline void flows_judge_lds(const FlowsArgs& a, FlowLds& L, uint32_t N2, uint32_t* status) {
+  const uint32_t tid = threadIdx.x, n = (uint32_t)a.n;
 
   // 2. sorted by slot, then by arrival; the flowless datagrams last
   for (uint32_t k = 2; k <= N2; k <<= 1) {
@@ -345,8 +355,22 @@ __device__ inline void flows_judge(const FlowsArgs& a, FlowLds& L) {
     a.info[5] = L.walked;
     a.info[6] = 0;
     a.info[7] = 0;
-    *a.status = L.bad ? RUDP_ST_FLOW : 0u;
+    if (status) *status = L.bad ? RUDP_ST_FLOW : 0u;
   }
+}
+
+// The whole call for one workgroup of kBlock threads (0 <= n <= kFlowMax).
+__device__ inline void flows_judge(const FlowsArgs& a, FlowLds& L) {
+  if (a.n == 0) {  // (uniform)
+    if (threadIdx.x < 8) a.info[threadIdx.x] = 0;
+    if (threadIdx.x == 0) *a.status = 0;
+    return;
+  }
+  const uint32_t N2 = flows_reset(L, (uint32_t)a.n);
+  __syncthreads();
+  flows_load(a, L, N2);
+  __syncthreads();
+  flows_judge_lds(a, L, N2, a.status);
 }
 
 }  // namespace rudp

@@ -427,6 +427,40 @@ struct RecvWindowArgs {
   uint32_t* carry_src;          // [n]: the frame of carry rank k
 };
 
+// rudp_receive_flows (receive_flows.hip): the decode's arguments, the rule's
+// (f reads the tables the decode writes), the ordered gather's, and the reply
+// and closing datagrams.
+struct RecvFlowsArgs {
+  const unsigned char* frames;  // moved back to a 16-B boundary by the C entry point
+  uint64_t fmis;                // distance of the caller's frames[0] from it (0..15)
+  uint64_t frames_bytes;        // size of the caller's buffer: the offset rule's limit
+  const uint64_t* frame_off;    // [n + 1]
+  const uint16_t* csum_in;      // rudp5 sideband, may be null
+  uint32_t H;
+  FlowsArgs f;                  // n, the slots, the table, and the tables the rule reads and writes (f.status: unused)
+  uint16_t* seq;
+  uint16_t* ack;
+  uint8_t* flags;
+  uint8_t* ok;
+  uint16_t* csum_out;           // may be null
+  uint8_t* valid;
+  uint8_t* usable;
+  uint32_t* chars;
+  unsigned char* payload;
+  uint64_t payload_cap;
+  uint64_t* payload_off;        // [n + 1]; [0..K] written
+  uint32_t* payload_src;        // [n], may be null
+  unsigned char* reply_frames;  // [n * H]; R * H bytes are written
+  uint16_t* reply_csum;         // [n], may be null
+  uint32_t* reply_index;        // [n]
+  unsigned char* fin_frames;    // [n * H]; E * H bytes are written
+  uint16_t* fin_csum;           // [n], may be null
+  uint32_t* fin_flow;           // [n]
+  uint64_t* info;               // [12]
+  uint32_t* status;
+  const uint32_t* words;        // chained form (set by the C entry point): the status of [0] the decode [1] the rule [2] the gather
+};
+
 // The sender's judgement of a reply batch (acknowledge.hip).
 struct AckArgs {
   const uint16_t* ack;
@@ -678,6 +712,10 @@ struct Tuning {
   // both buffers: the one-workgroup fused kernel (1; 2: also past its mean frame
   // length, for sweeps) or the chain of the join and the existing launches (0).
   RUDP_KNOB(receive_window_fused, 1)
+  // rudp_receive_flows of a batch of at most kRfFusedBytes bytes: the
+  // one-workgroup fused kernel (1; 2: also past its mean frame length, for
+  // sweeps) or the chain of the existing launches and the finishing pass (0).
+  RUDP_KNOB(receive_flows_fused, 1)
   RUDP_KNOB(host_slots, 3)     // *_host pipeline: device staging slots (2..8)
   RUDP_KNOB(host_stage_mb, 128)  // *_host pipeline: MiB per slot (1M x 1472 B pinned: 33 ms at 128 vs 94 ms at 32)
   RUDP_KNOB(host_min_chunks, 4)  // *_host pipeline: batches over 4 MiB go as at least this many chunks (copy overlap)
@@ -844,6 +882,15 @@ bool receive_window_fused_ok(uint64_t n_carried, uint64_t n_new, uint64_t total_
 int launch_receive_window_fused(RecvWindowArgs args, hipStream_t stream);
 int launch_recv_window_join(const RecvWindowArgs& args, hipStream_t stream);
 int launch_recv_window_finish(const RecvWindowArgs& args, hipStream_t stream);
+// rudp_receive_flows (receive_flows.hip).  The fused form: one workgroup takes
+// the batch from frames to every flow's message piece, the replies and the
+// closing datagrams through LDS, no scratch; receive_flows_fused_ok says whether
+// a batch takes it (n == 0 always does).  The chained form's own step: one
+// workgroup behind the existing launches that builds the replies and the
+// closing datagrams and completes info and status.
+bool receive_flows_fused_ok(uint64_t n, uint64_t frames_bytes);
+int launch_receive_flows_fused(const RecvFlowsArgs& args, hipStream_t stream);
+int launch_receive_flows_finish(const RecvFlowsArgs& args, hipStream_t stream);
 // rudp_ack_progress (acknowledge.hip): one launch for a batch of at most 1024
 // replies, else five with the tile maxima in the stream's scratch (inside a
 // ScratchCall).  rudp_acknowledge: the fused form (one workgroup from frames to

@@ -292,6 +292,8 @@ RUDP_API int rudpx_copy_vpt(const void* src, void* dst, uint64_t n16, int vpt, i
 //     its mean frame length) or chained (0).
 // 82: rudp_receive_window of at most 1024 new frames and kRwFusedBytes in the fused kernel (1; 2: also
 //     past its mean frame length) or chained (0).
+// 83: rudp_receive_flows of at most kRfFusedBytes in the fused kernel (1; 2: also past its mean frame
+//     length) or chained (0).
 // (72: a first-round stagger of half the fused decode tiles' workgroups (s_sleep),
 // 0.539 -> 0.540-0.543 ms on multi-byte text, ASCII 0.229 -> 0.231-0.233: removed;
 // profiles/r05/sweeps/utf8_decode_stagger.json.)
@@ -358,7 +360,8 @@ RUDP_API int rudpx_tune(int key, int value) {
             : key == 79 ? &t.accept_single
             : key == 80 ? &t.receive_fused
             : key == 81 ? &t.acknowledge_fused
-            : key == 82 ? &t.receive_window_fused : nullptr;
+            : key == 82 ? &t.receive_window_fused
+            : key == 83 ? &t.receive_flows_fused : nullptr;
   if (!slot) return -22;
   return slot->exchange(value);
 }

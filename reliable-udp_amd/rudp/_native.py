@@ -50,8 +50,9 @@ EXPORTS = (
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
     "rudp_gather_payloads", "rudp_segment_utf8", "rudp_payload_chars", "rudp_accept_inorder",
     "rudp_receive", "rudp_ack_progress", "rudp_acknowledge", "rudp_accept_window", "rudp_gather_ordered",
-    "rudp_receive_window", "rudp_accept_flows",
+    "rudp_receive_window", "rudp_accept_flows", "rudp_receive_flows",
 )
+HAS_RECEIVE_FLOWS = True  # RUDP_HAS_RECEIVE_FLOWS: rudp_receive_flows
 ACK_EXACT, ACK_CUMULATIVE = 0, 1  # RUDP_ACK_*: the mode of rudp_ack_progress / rudp_acknowledge
 
 
@@ -87,6 +88,16 @@ class RudpReceivedWindow(ctypes.Structure):
         (name, ctypes.c_void_p) for name in ("payload_off", "payload_src", "carry_frames")] + [
         ("carry_cap", ctypes.c_uint64)] + [(name, ctypes.c_void_p) for name in (
             "carry_off", "carry_csum", "reply_frames", "reply_csum", "reply_index", "reply_peer", "info", "status")]
+
+
+class RudpReceivedFlows(ctypes.Structure):
+    """struct rudp_received_flows (include/rudp.h): the output pointers of rudp_receive_flows."""
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "seq", "ack", "flags", "ok", "csum_out", "valid", "usable", "chars", "accept", "keep", "reply", "reply_ack",
+        "rank", "order", "order_off", "flow_info", "payload")] + [("payload_cap", ctypes.c_uint64)] + [
+        (name, ctypes.c_void_p) for name in (
+            "payload_off", "payload_src", "reply_frames", "reply_csum", "reply_index", "fin_frames", "fin_csum",
+            "fin_flow", "info", "status")]
 
 
 class RudpAcknowledged(ctypes.Structure):
@@ -143,6 +154,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rudp_accept_flows": [P, P, P, P, P, U64, P, U64, P, P, P, P, P, P, P, P, P, P, I, P],
         "rudp_receive_window": [P, U64, P, P, U64, P, U64, P, P, U64, U32, U32, U32, P,
                                 ctypes.POINTER(RudpReceivedWindow), I, I, P],
+        "rudp_receive_flows": [P, U64, P, U32, U64, P, P, P, U64, ctypes.POINTER(RudpReceivedFlows), I, I, P],
         "rudp_ack_progress": [P, P, P, P, U64, U32, U64, U32, I, U64, P, P, P, P, P, I, P],
         "rudp_acknowledge": [P, U64, P, U32, U64, P, U32, U64, U32, I, U64, P, ctypes.POINTER(RudpAcknowledged), I, I,
                              P],

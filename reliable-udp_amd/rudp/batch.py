@@ -1912,6 +1912,224 @@ def receive_flows(frames, frame_off, flow, layout: Union[str, int] = "rudp7", *,
     return ReceivedFlows(dec, usable, chars, acc, pieces)
 
 
+# The geometry of csrc/receive_flows.hip (tests/test_receive_flows_api.py holds these to the source).
+FLOWS_FUSED_BYTES = 32768   # rudp_receive_flows: a batch in at most this many bytes ...
+FLOWS_FUSED_MEAN = 133      # ... and this many per datagram is one launch of one workgroup
+_ST_FLOWS_FUSED = (_ST_ORDERED[0], _ST_MESSAGES[-1], _ST_ORDERED[2])  # offsets, flow slot, payload_cap
+
+
+class ReceivedFlowsFused:
+    """Result of ``receive_flows_fused``: one allocation, every member a view
+    of it, on the device.
+
+    Per datagram (N entries): ``seq``, ``ack``, ``csum``, ``reply_ack`` (u16),
+    ``flags``, ``ok``, ``valid``, ``usable``, ``accept``, ``keep``, ``reply``
+    (u8), ``chars`` (int32) and ``rank``, ``order`` (int32 holding u32 values)
+    as ``receive_flows`` returns them; ``order_off`` (int32 [N + 1]),
+    ``flow_info`` (int64 [N, 8]), ``payload`` (u8 [payload_cap]),
+    ``payload_off`` (int64 [N + 1]), ``payload_src`` (int32 [N]), ``info``
+    (int64 [12]: A, K, R, ended flows, datagrams without a flow, flows walked,
+    0, 0, message bytes, 0, 0, 0), ``status`` (int32 [1]) and ``states`` (the
+    caller's table, updated in place).  These never wait.
+
+    ``reply_frames`` (u8 [R * H]), ``reply_csum`` (u16 [R]), ``reply_index``
+    (int32 [R]: the datagram each reply answers, and whose source it goes to),
+    ``fin_frames`` (u8 [E * H]: the closing FIN|ACK of every flow that ended),
+    ``fin_csum`` (u16 [E]) and ``fin_flow`` (int32 [E]: its row of ``flows()``)
+    are cut to their counts.  They, ``active``, ``kept``, ``replies``,
+    ``ended``, ``flowless``, ``message_bytes``, ``flows()``, ``message(a)``,
+    ``host(name)`` (any table as a numpy array) and ``check()`` read the
+    device: one copy of the allocation, one synchronization, on first use."""
+
+    __slots__ = ("_buf", "_n", "_H", "_cap", "_lay", "_views", "_host", "states")
+    _TABLES = {  # name: (bytes per datagram, bytes on top, torch dtype name, numpy dtype)
+        "payload_off": (8, 8, "int64", np.int64), "flow_info": (64, 0, "int64", np.int64),
+        "info": (0, 96, "int64", np.int64), "status": (0, 8, "int32", np.int32),
+        "rank": (4, 0, "int32", np.int32), "order": (4, 0, "int32", np.int32),
+        "order_off": (4, 4, "int32", np.int32), "chars": (4, 0, "int32", np.int32),
+        "payload_src": (4, 0, "int32", np.int32), "reply_index": (4, 0, "int32", np.int32),
+        "fin_flow": (4, 0, "int32", np.int32),
+        "seq": (2, 0, "uint16", np.uint16), "ack": (2, 0, "uint16", np.uint16), "csum": (2, 0, "uint16", np.uint16),
+        "reply_ack": (2, 0, "uint16", np.uint16), "reply_csum": (2, 0, "uint16", np.uint16),
+        "fin_csum": (2, 0, "uint16", np.uint16),
+        "flags": (1, 0, "uint8", np.uint8), "ok": (1, 0, "uint8", np.uint8), "valid": (1, 0, "uint8", np.uint8),
+        "usable": (1, 0, "uint8", np.uint8), "accept": (1, 0, "uint8", np.uint8), "keep": (1, 0, "uint8", np.uint8),
+        "reply": (1, 0, "uint8", np.uint8),
+    }
+
+    def __init__(self, buf, n: int, H: int, cap: int, states):
+        self._buf, self._n, self._H, self._cap, self.states = buf, n, H, cap, states
+        self._lay = ReceivedFlowsFused.layout(n, H, cap)
+        self._views, self._host = {}, None
+
+    @staticmethod
+    def layout(n: int, H: int, cap: int):
+        """name -> (byte offset, bytes) in the one allocation, every array
+        aligned to its element (the payload to 16 bytes); ``size`` is the
+        allocation's."""
+        lay, at = {}, 0
+        for name, (per, top, _, _) in ReceivedFlowsFused._TABLES.items():
+            lay[name] = (at, per * n + top)
+            at += per * n + top
+        for name in ("reply_frames", "fin_frames"):
+            lay[name] = (at, n * H)
+            at += n * H
+        lay["payload"] = ((at + 15) & ~15, cap)
+        lay["size"] = lay["payload"][0] + cap
+        return lay
+
+    def _cut(self, name):
+        v = self._views.get(name)
+        if v is None:
+            import torch
+            lo, nbytes = self._lay[name]
+            v = self._buf[lo:lo + nbytes]
+            spec = ReceivedFlowsFused._TABLES.get(name)
+            if spec is not None:
+                v = v.view(getattr(torch, spec[2]))
+            if name == "flow_info":
+                v = v.view(self._n, 8)
+            elif name == "status":
+                v = v[:1]
+            self._views[name] = v
+        return v
+
+    def __getattr__(self, name):
+        if name in ReceivedFlowsFused._TABLES or name == "payload":
+            return self._cut(name)
+        raise AttributeError(name)
+
+    def _read(self):
+        if self._host is None:
+            whole = self._buf.cpu().numpy()
+            h = {}
+            for name, span in self._lay.items():
+                if name == "size":
+                    continue
+                lo, nbytes = span
+                spec = ReceivedFlowsFused._TABLES.get(name)
+                h[name] = whole[lo:lo + nbytes].view(spec[3] if spec else np.uint8)
+            h["flow_info"] = h["flow_info"].reshape(self._n, 8)
+            h["info"] = [int(v) for v in h["info"]]
+            self._host = h
+        return self._host
+
+    def host(self, name: str):
+        """Table ``name`` on the host (numpy, whole), from the one copy."""
+        return self._read()[name]
+
+    active = property(lambda self: self._read()["info"][0])
+    kept = property(lambda self: self._read()["info"][1])
+    replies = property(lambda self: self._read()["info"][2])
+    ended = property(lambda self: self._read()["info"][3])
+    flowless = property(lambda self: self._read()["info"][4])
+    message_bytes = property(lambda self: self._read()["info"][8])
+    reply_frames = property(lambda self: self._cut("reply_frames")[:self.replies * self._H])
+    reply_csum = property(lambda self: self._cut("reply_csum")[:self.replies])
+    reply_index = property(lambda self: self._cut("reply_index")[:self.replies])
+    fin_frames = property(lambda self: self._cut("fin_frames")[:self.ended * self._H])
+    fin_csum = property(lambda self: self._cut("fin_csum")[:self.ended])
+    fin_flow = property(lambda self: self._cut("fin_flow")[:self.ended])
+
+    def flows(self):
+        """int64 [A, 8] on the host, ascending by slot: slot, end, accepted,
+        msg_start, characters, isn, kept, rank base of every active flow."""
+        return self._read()["flow_info"][:self.active]
+
+    def message(self, a: int) -> bytes:
+        """The message piece of active flow ``a`` (row a of ``flows()``)."""
+        h = self._read()
+        base, kept = int(h["flow_info"][a][7]), int(h["flow_info"][a][6])
+        if not kept or self.message_bytes > self._cap:
+            return b""
+        off = h["payload_off"]
+        return h["payload"][int(off[base]):int(off[base + kept])].tobytes()
+
+    def check(self) -> "ReceivedFlowsFused":
+        """Raise ValueError if the device rejected a frame's offsets or a flow
+        slot, or the message did not fit."""
+        bits = int(self._read()["status"][0]) if self._n else 0
+        if bits:
+            msgs = [m for b, m in _ST_FLOWS_FUSED if bits & b] or [f"status {bits:#x}"]
+            if bits & _native.ST_PAYLOAD_CAP:
+                msgs.append(f"{self.message_bytes} bytes are needed, payload has {self._cap}")
+            raise ValueError("; ".join(msgs))
+        return self
+
+    def __len__(self) -> int:
+        return self._n
+
+
+def receive_flows_fused(frames, frame_off, flow, layout: Union[str, int] = "rudp7", *, states, csum=None,
+                        payload_cap=None, out=None, stream=None) -> ReceivedFlowsFused:
+    """``receive_flows``, the reply datagrams and the closing datagrams in one
+    library call (rudp_receive_flows; include/rudp.h states the contract), with
+    no torch operation in between.  A batch in at most ``FLOWS_FUSED_BYTES``
+    bytes (and ``FLOWS_FUSED_MEAN`` per datagram) is one kernel launch.
+
+    ``frames``, ``frame_off``, ``flow``, ``states`` and ``csum`` as
+    ``receive_flows`` takes them.  ``payload_cap``: bytes for the message
+    pieces (None: ``frames.numel()``, which always suffices).  ``out``: an
+    earlier result whose allocation is taken over when it is large enough.
+    Never waits; every table equals what ``receive_flows`` returns for the
+    same input."""
+    H = layout_header_len(layout)
+    for name, t in (("frames", frames), ("frame_off", frame_off), ("flow", flow), ("states", states)):
+        if not _is_torch(t):
+            raise TypeError(f"receive_flows_fused takes torch tensors on a HIP device (no host-memory form): {name}")
+    import torch
+    if out is not None and not isinstance(out, ReceivedFlowsFused):
+        raise TypeError("out must be an earlier receive_flows_fused result")
+    dev = frames.device
+    if dev.type != "cuda":
+        raise ValueError("receive_flows_fused runs on a HIP device")
+    _dev_check(frames, "frames", torch.uint8, 1, dev)
+    _int_tensor(frame_off, "frame_off", dev, dtypes=(torch.int64,))
+    n = frame_off.shape[0] - 1
+    if n < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    if n > FLOWS_MAX_BATCH:
+        raise ValueError(f"receive_flows_fused takes at most {FLOWS_MAX_BATCH} datagrams (one recvmmsg batch), got {n}")
+    _flows_tensor(flow, "flow", dev, (torch.int32,), n)
+    _flows_tensor(states, "states", dev, (torch.int64,), ndim=2)
+    if states.shape[1] != 4 or not 1 <= states.shape[0] <= 0xFFFFFFFE:
+        raise ValueError(f"states must be int64 [n_flows, 4] with 1 <= n_flows <= 2^32 - 2, got {tuple(states.shape)}")
+    if csum is not None:
+        if H == 7:
+            raise ValueError("rudp7 carries its checksum in-band; csum is for rudp5")
+        _dev_check(csum, "csum", torch.uint16, 1, dev)
+        if csum.shape[0] != n:
+            raise ValueError(f"csum has {csum.shape[0]} entries for {n} frames")
+    fbytes = frames.numel()
+    cap = fbytes if payload_cap is None else payload_cap
+    if isinstance(cap, bool) or not isinstance(cap, int) or cap < 0:
+        raise ValueError(f"payload_cap must be a non-negative int, got {payload_cap!r}")
+    lay = ReceivedFlowsFused.layout(n, H, cap)
+    if out is not None and out._buf.numel() >= lay["size"] and out._buf.device == dev:
+        buf = out._buf
+    else:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            buf = (torch.empty if n else torch.zeros)(lay["size"], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+
+    def tab(name, need=n):
+        return base + lay[name][0] if need else None
+
+    res = _native.RudpReceivedFlows(
+        seq=tab("seq"), ack=tab("ack"), flags=tab("flags"), ok=tab("ok"), csum_out=tab("csum"), valid=tab("valid"),
+        usable=tab("usable"), chars=tab("chars"), accept=tab("accept"), keep=tab("keep"), reply=tab("reply"),
+        reply_ack=tab("reply_ack"), rank=tab("rank"), order=tab("order"), order_off=tab("order_off"),
+        flow_info=tab("flow_info"), payload=tab("payload", cap), payload_cap=cap, payload_off=tab("payload_off"),
+        payload_src=tab("payload_src"), reply_frames=tab("reply_frames"), reply_csum=tab("reply_csum"),
+        reply_index=tab("reply_index"), fin_frames=tab("fin_frames"), fin_csum=tab("fin_csum"),
+        fin_flow=tab("fin_flow"), info=base + lay["info"][0], status=base + lay["status"][0])
+    _native.check(_native.lib().rudp_receive_flows(
+        frames.data_ptr() if fbytes else None, fbytes, frame_off.data_ptr(), min(fbytes // n, 0xFFFFFFFF) if n else 0,
+        n, csum.data_ptr() if csum is not None and n else None, flow.data_ptr() if n else None, states.data_ptr(),
+        states.shape[0], ctypes.byref(res), H, dev.index or 0, _stream_ptr(stream, dev)))
+    return ReceivedFlowsFused(buf, n, H, cap, states)
+
+
 class CarriedFrames:
     """The frames a ``receive_window`` call left pending, whole, on the device:
     pass it as ``carried=`` of the next call.  ``frames`` (u8) and ``frame_off``

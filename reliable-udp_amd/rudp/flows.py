@@ -95,9 +95,11 @@ class FlowReceiver:
     batch) and returns the transfers it completed; ``serve(count)`` polls until
     ``count`` messages are in.  ``table`` (``FlowTable``) and ``states`` (the
     device table) are the per-peer state; ``closing`` the slots whose FIN|ACK
-    still waits for the final ACK."""
+    still waits for the final ACK.  ``fused=True`` takes every batch through
+    the one library call (``batch.receive_flows_fused``): the replies and the
+    FIN|ACK datagrams come built from the device, one read per batch."""
 
-    def __init__(self, sock, device, max_flows: int = 1024, layout="rudp5"):
+    def __init__(self, sock, device, max_flows: int = 1024, layout="rudp5", fused: bool = False):
         import torch
         from . import netio
         self.sock, self.layout, self.H = sock, layout, layout_header_len(layout)
@@ -108,6 +110,7 @@ class FlowReceiver:
                                       device=self.device, with_sources=True)
         self.closing: Dict[int, _Closing] = {}
         self._parts: Dict[int, List[bytes]] = {}
+        self.fused = bool(fused)
 
     def _send_to(self, frame: bytes, key: int) -> None:
         from . import netio
@@ -127,6 +130,59 @@ class FlowReceiver:
         else:
             self._release(slot)
 
+    def _answer_closing(self, slots, seq, ack, flags, usable, now: float) -> None:
+        """What the batch's datagrams mean for the slots whose FIN|ACK waits:
+        the final ACK releases the slot; a datagram without ACK, or the closed
+        transfer's SYN again, has the FIN|ACK sent again."""
+        for slot, c in list(self.closing.items()):
+            mine = np.flatnonzero((slots == slot) & usable)
+            mine = mine[mine > c.after]
+            c.after = -1
+            resend = False
+            for i in mine.tolist():
+                f = int(flags[i])
+                if f & ACK and not f & SYN and int(ack[i]) == 1:  # the handshake is complete
+                    self._release(slot)
+                    resend = False
+                    break
+                if not f & ACK or (f & SYN and int(seq[i]) == c.isn):
+                    resend = True
+            if resend:
+                self._resend(slot, c, now)
+
+    def _poll_fused(self, n: int, done) -> None:
+        """One batch through ``batch.receive_flows_fused``: one read of the
+        result; the replies and the closing datagrams go out as the device
+        built them."""
+        from . import netio
+        sources = self.rx.sources.copy()
+        slots = self.table.slots(sources)
+        res, _, _ = self.rx.receive_flows_fused(slots, self.layout, states=self.states)
+        rows, H = res.flows(), self.H  # (the one wait per batch; every host read below is of the same copy)
+        R, E = res.replies, res.ended
+        if R:
+            netio.send_batch_to(self.sock, res.host("reply_frames")[:R * H], H * np.arange(R + 1, dtype=np.int64),
+                                sources[res.host("reply_index")[:R]])
+        fin = {int(a): res.host("fin_frames")[e * H:(e + 1) * H].tobytes()
+               for e, a in enumerate(res.host("fin_flow")[:E].tolist())}
+        now = time.monotonic()
+        for a in range(rows.shape[0]):
+            slot, end, _, msg_start, _, isn, kept, _ = (int(v) for v in rows[a])
+            if msg_start < n:  # a new transfer of this peer started in the batch
+                self._parts[slot] = []
+                self.closing.pop(slot, None)
+            if kept:
+                self._parts.setdefault(slot, []).append(res.message(a))
+            if end < n:
+                text = b"".join(self._parts.pop(slot, [])).decode()
+                key = self.table.key_of(slot)
+                done.append((netio.key_addr(key), text))
+                self._send_to(fin[a], key)
+                self.closing[slot] = _Closing(fin[a], isn, now + FIN_WAIT_S, end)
+        if self.closing:
+            self._answer_closing(slots, res.host("seq"), res.host("ack"), res.host("flags"),
+                                 res.host("usable") != 0, now)
+
     def poll(self, timeout_ms: int = -1) -> List[Tuple[Tuple[str, int], str]]:
         from . import netio
         import torch
@@ -138,7 +194,9 @@ class FlowReceiver:
         self.sock.setblocking(True)
         n = self.rx.recv(timeout_ms=wait)
         done: List[Tuple[Tuple[str, int], str]] = []
-        if n:
+        if n and self.fused:
+            self._poll_fused(n, done)
+        elif n:
             sources = self.rx.sources.copy()
             slots = self.table.slots(sources)
             res, _, _ = self.rx.receive_flows(slots, self.layout, states=self.states)
@@ -164,25 +222,9 @@ class FlowReceiver:
                     self.closing[slot] = _Closing(fin, isn, now + FIN_WAIT_S, end)
             if self.closing:
                 dec = res.decoded
-                seq = dec.seq.view(torch.int16).cpu().numpy().view(np.uint16)
-                ack = dec.ack.view(torch.int16).cpu().numpy().view(np.uint16)
-                flags = dec.flags.cpu().numpy()
-                usable = res.usable.cpu().numpy() != 0
-                for slot, c in list(self.closing.items()):
-                    mine = np.flatnonzero((slots == slot) & usable)
-                    mine = mine[mine > c.after]
-                    c.after = -1
-                    resend = False
-                    for i in mine.tolist():
-                        f = int(flags[i])
-                        if f & ACK and not f & SYN and int(ack[i]) == 1:  # the handshake is complete
-                            self._release(slot)
-                            resend = False
-                            break
-                        if not f & ACK or (f & SYN and int(seq[i]) == c.isn):
-                            resend = True
-                    if resend:
-                        self._resend(slot, c, now)
+                self._answer_closing(slots, dec.seq.view(torch.int16).cpu().numpy().view(np.uint16),
+                                     dec.ack.view(torch.int16).cpu().numpy().view(np.uint16), dec.flags.cpu().numpy(),
+                                     res.usable.cpu().numpy() != 0, now)
         now = time.monotonic()
         for slot, c in list(self.closing.items()):
             if now >= c.deadline:  # FIN_WAIT_S without the final ACK

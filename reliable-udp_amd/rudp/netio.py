@@ -374,6 +374,47 @@ class BatchReceiver:
             t.record_stream(cur)
         return res, d_frames, d_off
 
+    def receive_flows_fused(self, flow, layout="rudp5", *, states, csum=None, out=None, stream=None):
+        """``receive_flows`` with the one library call
+        (``batch.receive_flows_fused``): the same H2D and bookkeeping, then the
+        batch judged for all its peers, the message pieces, the replies and
+        the closing datagrams in one call.  ``out``: an earlier result whose
+        allocation is taken over.  Never waits for the device.
+
+        Returns ``(ReceivedFlowsFused, d_frames, d_frame_off)``; reply k
+        answers datagram ``res.reply_index[k]`` and goes to that datagram's
+        source; closing datagram e goes to the peer of slot
+        ``res.flows()[res.fin_flow[e]][0]``."""
+        import torch
+        s = stream if stream is not None else self.stream
+        k, n = self._slot, self.count
+        if k < 0:
+            raise RuntimeError("receive_flows_fused() before any recv()")
+        flow = np.ascontiguousarray(flow, dtype=np.uint32)
+        if flow.shape != (n,):
+            raise ValueError(f"flow has shape {flow.shape} for {n} datagrams")
+        total = int(self._off_t[k][n])
+        h_flow = torch.from_numpy(flow.view(np.int32)).pin_memory()
+        s.wait_stream(torch.cuda.current_stream(self.device))  # e.g. csum or states written by the caller
+        with torch.cuda.stream(s):
+            d_frames = torch.empty((total,), dtype=torch.uint8, device=self.device)
+            d_off = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+            d_flow = torch.empty((n,), dtype=torch.int32, device=self.device)
+            d_frames.copy_(self._frames_t[k][:total], non_blocking=True)
+            d_off.copy_(self._off_t[k][:n + 1], non_blocking=True)
+            d_flow.copy_(h_flow, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(s)
+            self._copied[k] = ev
+            res = _batch.receive_flows_fused(d_frames, d_off, d_flow, layout, states=states, csum=csum, out=out,
+                                             stream=s)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(s)
+        # allocated on `s`, used on the caller's stream from here on
+        for t in (d_frames, d_off, d_flow, res._buf):  # the result's members are views of one buffer
+            t.record_stream(cur)
+        return res, d_frames, d_off
+
     def acknowledge(self, layout="rudp5", *, isn, total_chars, chunk=1, state=None, mode="exact", sent=None,
                     csum=None, stream=None):
         """H2D of the received reply datagrams as ``receive()`` does it (the same

@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--L", default="1472,1024,64")
     ap.add_argument("--reps", type=int, default=11)
     ap.add_argument("--op", default="encode", choices=["encode", "decode", "varlen", "vdecode", "vu8", "vval", "u8text",
-                                                       "u8ascii", "u8val", "u8valtext", "accept"],
+                                                       "u8ascii", "u8val", "u8valtext", "accept", "flows"],
                     help="decode: verify-only fixed-length rudp_decode of the encoded frames; varlen: "
                          "rudp_encode_varlen_checked of packed payloads, --L lengths or 'ragged' "
                          "(uniform in [0, 2944]); a 'u' suffix (1472u) times the unchecked rudp_encode_varlen; "
@@ -39,7 +39,9 @@ def main():
                          "sideband checksums below 16-B payloads, else rudp7; u8text: rudp_decode_utf8 of "
                          "frames whose payload is valid multi-byte UTF-8 text (1-4 byte characters); u8ascii: "
                          "rudp_decode_utf8 of the ASCII synthetic frames; u8val / u8valtext: rudp_validate_utf8 (the check alone) of the ASCII / text frames; accept: rudp_accept_inorder of a "
-                         "clean stop-and-wait stream of --L datagrams (1024: one recvmmsg batch, one launch)")
+                         "clean stop-and-wait stream of --L datagrams (1024: one recvmmsg batch, one launch); flows: "
+                         "rudp_accept_flows of 1024 datagrams of --L clean flows (1, 37, 1024), the table reset by a "
+                         "device copy before every call (timed with the call, the same for every build)")
     args = ap.parse_args()
     _native.lib()  # torch's HIP runtime first
     libs = {}
@@ -81,10 +83,20 @@ def main():
             h.rudp_accept_inorder.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint64, ctypes.c_uint32] + \
                 [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_void_p]
             h.rudp_accept_inorder.restype = ctypes.c_int
+        if hasattr(h, "rudp_accept_flows"):
+            h.rudp_accept_flows.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64] + \
+                [ctypes.c_void_p] * 10 + [ctypes.c_int, ctypes.c_void_p]
+            h.rudp_accept_flows.restype = ctypes.c_int
         libs[name] = h
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream().cuda_stream
     out = {}
+    if args.op == "flows":
+        for spec in args.L.split(","):
+            out[spec] = flows_ab(libs, int(spec), args.reps, dev, stream)
+            print(spec, out[spec], file=sys.stderr, flush=True)
+        print(json.dumps(out, indent=1))
+        return
     if args.op == "accept":
         for spec in args.L.split(","):
             out[spec] = accept_ab(libs, int(spec), args.reps, dev, stream)
@@ -297,6 +309,44 @@ def accept_ab(libs, n, reps, dev, stream):
             times[name].append(s.elapsed_time(e) / inner)
     return {"ms": {k: statistics.median(v) for k, v in times.items()},
             "ms_min_max": {k: [min(v), max(v)] for k, v in times.items()}, "exact": exact}
+
+
+def flows_ab(libs, n_active, reps, dev, stream):
+    """rudp_accept_flows of one 1024-datagram batch of n_active clean flows (tools/flows_probe.py's batch)."""
+    sys.path[:0] = [str(REPO / "tests"), str(REPO / "tools")]
+    from flows_probe import N, flow_batch
+    _, d = flow_batch(n_active, dev, 0xF10 + n_active)
+    lay = batch.FlowsAccepted.layout(N)
+    outs = torch.zeros(lay["size"], dtype=torch.uint8, device=dev)
+    pristine = torch.zeros((N, 4), dtype=torch.int64, device=dev)
+    states = torch.zeros((N, 4), dtype=torch.int64, device=dev)
+    at = [outs.data_ptr() + lay[k] for k in ("accept", "keep", "reply", "reply_ack", "rank", "order", "order_off",
+                                             "flow_info", "info", "status")]
+
+    def call(h):
+        states.copy_(pristine)
+        return h.rudp_accept_flows(*(t.data_ptr() for t in d), N, states.data_ptr(), N, *at, 0, stream)
+    ref, exact = None, {}
+    for name, h in libs.items():
+        outs.zero_()
+        assert call(h) == 0
+        got = torch.cat((outs, states.view(torch.uint8).flatten()))
+        ref = got if ref is None else ref
+        exact[name] = bool(torch.equal(got, ref))
+    times = {k: [] for k in libs}
+    for _ in range(reps):
+        for name, h in libs.items():
+            for _ in range(2):
+                call(h)
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(200):
+                call(h)
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / 200)
+    return {"us_with_reset": {k: statistics.median(v) for k, v in times.items()},
+            "us_min_max": {k: [min(v), max(v)] for k, v in times.items()}, "exact": exact}
 
 
 def text_flat(lens, dev):

@@ -1041,6 +1041,90 @@ RUDP_API int rudp_acknowledge(const uint8_t* d_frames, uint64_t frames_bytes, co
                               void* hip_stream);
 
 /*
+ * One reply batch judged for many transfers (added within ABI 8,
+ * RUDP_HAS_ACK_FLOWS): rudp_ack_progress' rule for the reply datagrams of many
+ * concurrent sends, the mirror image of rudp_accept_flows.  One call judges a
+ * batch of at most RUDP_FLOWS_MAX_BATCH replies in one launch, with every
+ * per-transfer constant and state in a device table.  Sync-free: asynchronous
+ * on hip_stream, the host never waits, no temporaries, usable under stream
+ * capture, no work proportional to the table.
+ *
+ * d_seq, d_ack, d_flags, d_usable_or_null and n as rudp_ack_progress takes
+ * them; d_flow[i] (u32) is the slot of reply i's peer; mode is RUDP_ACK_EXACT
+ * or RUDP_ACK_CUMULATIVE, for the whole call.  d_states is u64[n_flows][8],
+ * read and written in place; a row is {p, L, last, done, isn, T, C, sent}:
+ * words 0 to 3 are rudp_ack_progress' state, words 4 to 7 its scalars isn,
+ * total_chars, chunk_chars and sent_chars.  The call writes only words 0 to 3,
+ * and only of rows whose slot occurs in the batch; the host owns words 4 to 7
+ * (in CUMULATIVE mode it updates sent of the flows it has sent to before the
+ * call; sent is not read in EXACT mode).  A fresh transfer's row is
+ * {0, min(C, T), L == T, 0, isn, T, C, 0}.
+ *
+ * Per slot the rule is exactly rudp_ack_progress' (its text above is the
+ * definition, the quirks kept from the reference included), applied to the
+ * slot's replies in arrival order with the row as d_state_in and as the
+ * scalars, the slots independently.  Ignored: a reply with d_flow[i] ==
+ * RUDP_FLOW_NONE; one with d_flow[i] >= n_flows, which sets RUDP_ST_FLOW; one
+ * whose row has C == 0, an idle slot (an all-zero table is a table of idle
+ * slots), silently; one whose row has isn > 65535, C > 16383 or, in
+ * CUMULATIVE mode, sent > T, which sets RUDP_ST_FLOW_ROW.  An ignored reply
+ * gets every per-reply output 0 and touches no row; the flow of an ignored row
+ * is not among the active flows, and its replies go with the flowless ones in
+ * d_order.  A flow whose row has done set on entry is listed but not judged:
+ * valid = 0, end = n, the row unchanged.  A flow's first valid FIN ends it at
+ * arrival index end_f: done becomes 1 and its later replies in this call are
+ * not judged.
+ *
+ * Per-reply outputs, n entries each, in arrival order:
+ *   d_valid[i]    u8: valid_i
+ *   d_pointer[i]  u64: p of that reply's flow after the reply; 0 where the
+ *                 reply was not judged
+ * Grouping outputs, A = the distinct slots of the batch that were judged or
+ * found done:
+ *   d_order[n], d_order_off[0..A]
+ *                 as rudp_accept_flows defines them: flow-major, ascending
+ *                 slot, arrival order within a slot, the rest last (provide
+ *                 n + 1 entries of d_order_off)
+ *   d_flow_info   u64[A][8], ascending by slot (provide n rows): [0] slot
+ *                 [1] end (arrival index; n: none) [2] valid replies
+ *                 [3] characters newly acknowledged [4] p after [5] the next
+ *                 frame index ceil(p / C) [6] done after [7] for a flow with
+ *                 end < n closing_seq | closing_ack << 16, else 0:
+ *                 closing_seq = (isn + p) mod 2^16 and closing_ack =
+ *                 (seq_end + 1) mod 2^16, rudp_acknowledge's closing datagram
+ *   d_info        u64[8]: [0] A [1] valid replies in all [2] E, the flows that
+ *                 ended in this call [3] characters newly acknowledged in all
+ *                 [4] replies outside the A runs [5] flows the kernel judged
+ *                 sequentially (a diagnostic, not part of the contract)
+ *                 [6..7] 0
+ *   *d_status     required: 0, or RUDP_ST_FLOW | RUDP_ST_FLOW_ROW
+ * Closing datagrams, with final_layout 5 or 7: d_final_frames receives E
+ * datagrams of final_layout bytes at that stride, for the flows with end < n
+ * in ascending slot order, each with flags 0x40, the fields above and, for
+ * layout 7, its RFC 1071 checksum in-band; d_final_csum_or_null u16[E], the
+ * checksums; d_final_flow u32[E], the index a into d_flow_info.  Provide n *
+ * final_layout bytes and n entries; nothing is written at or past E *
+ * final_layout.  With final_layout 0 these pointers may be NULL and nothing is
+ * built.
+ * Nothing is written past index A of d_order_off or past row A - 1 of
+ * d_flow_info.  n == 0 writes d_info = 0 and *d_status = 0 and touches nothing
+ * else.  n > RUDP_FLOWS_MAX_BATCH returns RUDP_ENOTSUP.  RUDP_EINVAL before any
+ * HIP call: d_states, d_info or d_status NULL; n_flows 0 or above 2^32 - 2; a
+ * mode other than the two; a final_layout other than 0, 5 or 7; with n > 0,
+ * any other pointer NULL except d_usable_or_null, d_final_csum_or_null and,
+ * with final_layout 0, the final tables.
+ */
+#define RUDP_HAS_ACK_FLOWS 1
+#define RUDP_ST_FLOW_ROW 512u /* ack_flows: a row with isn > 65535, C > 16383 or (CUMULATIVE) sent > T */
+RUDP_API int rudp_ack_flows(const uint16_t* d_seq, const uint16_t* d_ack, const uint8_t* d_flags,
+                            const uint8_t* d_usable_or_null, const uint32_t* d_flow, uint64_t n, int mode,
+                            uint64_t* d_states, uint64_t n_flows,
+                            uint8_t* d_valid, uint64_t* d_pointer, uint32_t* d_order, uint32_t* d_order_off,
+                            uint64_t* d_flow_info, uint64_t* d_info, uint32_t* d_status,
+                            int final_layout, uint8_t* d_final_frames, uint16_t* d_final_csum_or_null,
+                            uint32_t* d_final_flow, int device, void* hip_stream);
+
+/*
  * Bounds of a variable-length batch, computed on the device (argument checks
  * the varlen entry points need before they can size or trust a buffer; the
  * reference has no batch and so no counterpart).  Synchronous on hip_stream.

@@ -1787,6 +1787,69 @@ int rudp_acknowledge(const uint8_t* d_frames, uint64_t frames_bytes, const uint6
   return 0;
 }
 
+int rudp_ack_flows(const uint16_t* d_seq, const uint16_t* d_ack, const uint8_t* d_flags,
+                   const uint8_t* d_usable_or_null, const uint32_t* d_flow, uint64_t n, int mode, uint64_t* d_states,
+                   uint64_t n_flows, uint8_t* d_valid, uint64_t* d_pointer, uint32_t* d_order, uint32_t* d_order_off,
+                   uint64_t* d_flow_info, uint64_t* d_info, uint32_t* d_status, int final_layout,
+                   uint8_t* d_final_frames, uint16_t* d_final_csum_or_null, uint32_t* d_final_flow, int device,
+                   void* hip_stream) {
+  if (!d_states) return fail(RUDP_EINVAL, "rudp_ack_flows: d_states is NULL");
+  if (!d_info) return fail(RUDP_EINVAL, "rudp_ack_flows: d_info is NULL");
+  if (!d_status) return fail(RUDP_EINVAL, "rudp_ack_flows: d_status is NULL");
+  if (n_flows < 1u || n_flows > 0xFFFFFFFEull)
+    return fail(RUDP_EINVAL, "rudp_ack_flows: n_flows %llu outside [1, 2^32 - 2]", (unsigned long long)n_flows);
+  if (mode != RUDP_ACK_EXACT && mode != RUDP_ACK_CUMULATIVE)
+    return fail(RUDP_EINVAL, "rudp_ack_flows: mode %d (use RUDP_ACK_EXACT or RUDP_ACK_CUMULATIVE)", mode);
+  if (final_layout != 0 && final_layout != RUDP_LAYOUT_RUDP5 && final_layout != RUDP_LAYOUT_RUDP7)
+    return fail(RUDP_EINVAL, "rudp_ack_flows: final_layout %d (use 0, RUDP_LAYOUT_RUDP5 or RUDP_LAYOUT_RUDP7)",
+                final_layout);
+  if (n > RUDP_FLOWS_MAX_BATCH)
+    return fail(RUDP_ENOTSUP, "rudp_ack_flows: n %llu exceeds RUDP_FLOWS_MAX_BATCH (%u replies, one recvmmsg batch)",
+                (unsigned long long)n, RUDP_FLOWS_MAX_BATCH);
+  if (n) {
+    if (!d_seq) return fail(RUDP_EINVAL, "rudp_ack_flows: d_seq is NULL");
+    if (!d_ack) return fail(RUDP_EINVAL, "rudp_ack_flows: d_ack is NULL");
+    if (!d_flags) return fail(RUDP_EINVAL, "rudp_ack_flows: d_flags is NULL");
+    if (!d_flow) return fail(RUDP_EINVAL, "rudp_ack_flows: d_flow is NULL");
+    if (!d_valid) return fail(RUDP_EINVAL, "rudp_ack_flows: d_valid is NULL");
+    if (!d_pointer) return fail(RUDP_EINVAL, "rudp_ack_flows: d_pointer is NULL");
+    if (!d_order) return fail(RUDP_EINVAL, "rudp_ack_flows: d_order is NULL");
+    if (!d_order_off) return fail(RUDP_EINVAL, "rudp_ack_flows: d_order_off is NULL");
+    if (!d_flow_info) return fail(RUDP_EINVAL, "rudp_ack_flows: d_flow_info is NULL");
+    if (final_layout) {
+      if (!d_final_frames) return fail(RUDP_EINVAL, "rudp_ack_flows: d_final_frames is NULL");
+      if (!d_final_flow) return fail(RUDP_EINVAL, "rudp_ack_flows: d_final_flow is NULL");
+    }
+  }
+  DeviceScope dev_scope;
+  int rc = dev_scope.set(device);
+  if (rc) return rc;
+  AckFlowsArgs a{};
+  a.seq = d_seq;
+  a.ack = d_ack;
+  a.flags = d_flags;
+  a.usable = d_usable_or_null;
+  a.flow = d_flow;
+  a.n = n;
+  a.mode = (uint32_t)mode;
+  a.H = (uint32_t)final_layout;
+  a.states = d_states;
+  a.n_flows = n_flows;
+  a.valid = d_valid;
+  a.pointer = d_pointer;
+  a.order = d_order;
+  a.order_off = d_order_off;
+  a.flow_info = d_flow_info;
+  a.info = d_info;
+  a.status = d_status;
+  a.final_frames = d_final_frames;
+  a.final_csum = final_layout ? d_final_csum_or_null : nullptr;
+  a.final_flow = d_final_flow;
+  rc = launch_ack_flows(a, (hipStream_t)hip_stream);
+  if (rc) return hip_fail((hipError_t)rc, "flows acknowledgement launch");
+  return 0;
+}
+
 int rudp_varlen_bounds(const uint32_t* d_len, const int64_t* d_payload_off_or_null, uint64_t n,
                        int64_t* h_out, int device, void* hip_stream) {
   if (!h_out) return fail(RUDP_EINVAL, "rudp_varlen_bounds: h_out is NULL");

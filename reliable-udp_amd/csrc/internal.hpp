@@ -480,6 +480,30 @@ struct AckArgs {
   uint64_t* hdr;                // more than one tile: the call's scratch (set by the launcher)
 };
 
+// One reply batch judged for many transfers (ack_flows.hip).
+struct AckFlowsArgs {
+  const uint16_t* seq;
+  const uint16_t* ack;
+  const uint8_t* flags;
+  const uint8_t* usable;        // [n], or null: every reply usable
+  const uint32_t* flow;         // [n]: the slot of each reply's peer, or RUDP_FLOW_NONE
+  uint64_t n;                   // at most RUDP_FLOWS_MAX_BATCH
+  uint32_t mode;                // RUDP_ACK_EXACT or RUDP_ACK_CUMULATIVE
+  uint32_t H;                   // final_layout: 0, 5 or 7
+  uint64_t* states;             // [n_flows][8], words 0 to 3 in place
+  uint64_t n_flows;
+  uint8_t* valid;
+  uint64_t* pointer;
+  uint32_t* order;              // [n]
+  uint32_t* order_off;          // [n + 1]; [0..A] written
+  uint64_t* flow_info;          // [n][8]; A rows written
+  uint64_t* info;               // [8]
+  uint32_t* status;
+  unsigned char* final_frames;  // [n * H]; E * H bytes are written (H != 0)
+  uint16_t* final_csum;         // [n], may be null
+  uint32_t* final_flow;         // [n]
+};
+
 // Reply datagrams to sender state and closing datagram (acknowledge.hip): the
 // decode's arguments, the rule's (r reads the tables the decode writes) and
 // the closing frame.
@@ -902,6 +926,8 @@ bool acknowledge_fused_ok(uint64_t n, uint64_t frames_bytes);
 int launch_acknowledge_fused(const AcknowledgeArgs& args, hipStream_t stream);
 int launch_ack_usable(const uint8_t* ok, uint8_t* usable, uint64_t n, hipStream_t stream);
 int launch_ack_final_frame(const AcknowledgeArgs& args, hipStream_t stream);
+// rudp_ack_flows (ack_flows.hip): one launch of one workgroup.
+int launch_ack_flows(const AckFlowsArgs& args, hipStream_t stream);
 // Span starts for the byte-tiled varlen encode: rec[k] (k = 0 .. count) holds
 // p, the first packet whose packed payload starts at or after k * bytes, and
 // fo = frame_off[p], so a tile has its packet range and frame run from two

@@ -27,7 +27,7 @@ INCLUDE = ROOT.parent / "include"
 BUILD = ROOT / "build"
 LIB = PKG_DIR / "librudp.so"
 TOOLS_LIB = PKG_DIR / "librudp_tools.so"
-SOURCES = ("encode.hip", "decode.hip", "synth.hip", "varlen.hip", "dedup.hip", "bounds.hip", "scan.hip", "gather.hip", "segment.hip", "accept.hip", "window.hip", "flows.hip", "ordered.hip", "receive.hip", "receive_window.hip", "receive_flows.hip", "acknowledge.hip", "device_pool.hip", "capi.hip",
+SOURCES = ("encode.hip", "decode.hip", "synth.hip", "varlen.hip", "dedup.hip", "bounds.hip", "scan.hip", "gather.hip", "segment.hip", "accept.hip", "window.hip", "flows.hip", "ordered.hip", "receive.hip", "receive_window.hip", "receive_flows.hip", "acknowledge.hip", "ack_flows.hip", "device_pool.hip", "capi.hip",
            "tuning.hip", "netio.cpp")
 ARCH = "gfx950"
 

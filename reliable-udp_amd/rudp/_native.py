@@ -32,6 +32,7 @@ ST_PACKETS_CAP = 32  # rudp_segment_utf8: more packets than the tables hold
 ST_RANK = 64  # rudp_gather_ordered: a rank at or above the count that is not RANK_NONE
 ST_CARRY_CAP = 128  # rudp_receive_window: the pending frames need more than carry_cap bytes
 ST_FLOW = 256  # rudp_accept_flows: a d_flow[i] at or above n_flows that is not FLOW_NONE
+ST_FLOW_ROW = 512  # rudp_ack_flows: a row with isn > 65535, C > 16383 or (cumulative) sent > T
 FLOW_NONE = 0xFFFFFFFF  # RUDP_FLOW_NONE: a datagram without a flow
 FLOWS_MAX_BATCH = 1024  # RUDP_FLOWS_MAX_BATCH
 RANK_NONE = 0xFFFFFFFF  # RUDP_RANK_NONE
@@ -50,7 +51,7 @@ EXPORTS = (
     "rudp_decode_varlen_host", "rudp_encode_varlen_host",
     "rudp_gather_payloads", "rudp_segment_utf8", "rudp_payload_chars", "rudp_accept_inorder",
     "rudp_receive", "rudp_ack_progress", "rudp_acknowledge", "rudp_accept_window", "rudp_gather_ordered",
-    "rudp_receive_window", "rudp_accept_flows", "rudp_receive_flows",
+    "rudp_receive_window", "rudp_accept_flows", "rudp_receive_flows", "rudp_ack_flows",
 )
 HAS_RECEIVE_FLOWS = True  # RUDP_HAS_RECEIVE_FLOWS: rudp_receive_flows
 ACK_EXACT, ACK_CUMULATIVE = 0, 1  # RUDP_ACK_*: the mode of rudp_ack_progress / rudp_acknowledge
@@ -156,6 +157,7 @@ def _declare(lib: ctypes.CDLL) -> None:
                                 ctypes.POINTER(RudpReceivedWindow), I, I, P],
         "rudp_receive_flows": [P, U64, P, U32, U64, P, P, P, U64, ctypes.POINTER(RudpReceivedFlows), I, I, P],
         "rudp_ack_progress": [P, P, P, P, U64, U32, U64, U32, I, U64, P, P, P, P, P, I, P],
+        "rudp_ack_flows": [P, P, P, P, P, U64, I, P, U64, P, P, P, P, P, P, P, I, P, P, P, I, P],
         "rudp_acknowledge": [P, U64, P, U32, U64, P, U32, U64, U32, I, U64, P, ctypes.POINTER(RudpAcknowledged), I, I,
                              P],
         "rudp_dedup_stream_create": [U32, U32, U32, I, P, ctypes.POINTER(ctypes.c_void_p)],

@@ -2824,6 +2824,275 @@ def acknowledge(frames, frame_off, layout: Union[str, int] = "rudp7", *, isn: in
     return Acknowledged(buf, n, H)
 
 
+# ------------------------------------------------------------ replies of many transfers
+_ST_ACK_FLOWS = (_ST_MESSAGES[-1],  # a flow slot out of range
+                 (_native.ST_FLOW_ROW, "a row of the states table has isn > 65535, chunk > 16383 or sent > total_chars"))
+
+
+def _raise_bits(bits: int, messages) -> None:
+    if bits:
+        raise ValueError("; ".join(m for b, m in messages if bits & b) or f"status {bits:#x}")
+
+
+def ack_flow_states(n_flows: int, device):
+    """The zero table of ``n_flows`` idle slots for ``ack_flows``: int64
+    [n_flows, 8] on ``device``, a row {p, L, last, done, isn, T, C, sent}."""
+    import torch
+    if isinstance(n_flows, bool) or not isinstance(n_flows, int) or not 1 <= n_flows <= 0xFFFFFFFE:
+        raise ValueError(f"n_flows must be an int in [1, 2^32 - 2], got {n_flows!r}")
+    return torch.zeros((n_flows, 8), dtype=torch.int64, device=device)
+
+
+def ack_flow_open(states, slot: int, isn: int, total_chars: int, chunk: int = 1):
+    """Open ``slot`` of an ``ack_flow_states`` table for a fresh transfer: the
+    row {0, min(C, T), L == T, 0, isn, T, C, 0}, written in stream order."""
+    import torch
+    if not _is_torch(states) or states.dtype != torch.int64 or states.dim() != 2 or states.shape[1] != 8:
+        raise TypeError("states must be the int64 [n_flows, 8] table of ack_flow_states")
+    if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < states.shape[0]:
+        raise ValueError(f"slot must be an int in [0, {states.shape[0]}), got {slot!r}")
+    chunk, _, _ = _ack_scalars(isn, total_chars, chunk, "exact", None)
+    if total_chars >= 1 << 63:
+        raise ValueError(f"total_chars must be below 2^63, got {total_chars}")
+    row = list(fresh_ack_state(total_chars, chunk)) + [isn, total_chars, chunk, 0]
+    states[slot] = torch.tensor(row, dtype=torch.int64).to(states.device, non_blocking=True)
+    return states
+
+
+class AckFlows:
+    """Result of ``ack_flows``: one device buffer with cut views.  ``valid``
+    (u8 [N]), ``pointer`` (int64 [N]), ``order`` (int32 [N]), ``order_off``
+    (int32 [N + 1], of which [0..A] are written), ``flow_info`` (int64 [N, 8],
+    A rows written), ``info`` (int64 [8]: A, valid replies, ended flows,
+    characters newly acknowledged, replies outside every run, flows walked, 0,
+    0), ``status`` (int32 [1]), and with a ``final_layout`` ``final_frames``
+    (u8 [N, H], E rows written), ``final_csum`` (u16 [N]) and ``final_flow``
+    (int32 [N]) as rudp_ack_flows defines them; ``states`` is the caller's
+    table, updated in place.  ``active``, ``count``, ``ended``,
+    ``newly_acknowledged``, ``flowless``, ``flows()``, ``finals()`` and
+    ``check()`` read the device once, one synchronization for all; nothing else
+    waits."""
+
+    __slots__ = ("_buf", "_n", "_H", "_lay", "_views", "_host", "states")
+
+    def __init__(self, buf, n: int, H: int, states):
+        self._buf, self._n, self._H, self._lay, self.states = buf, n, H, AckFlows.layout(n, H), states
+        self._views, self._host = {}, None
+
+    @staticmethod
+    def layout(n: int, H: int):
+        """Byte offsets in the one allocation: pointer (u64 [n]) | flow_info
+        (u64 [n][8]) | info (u64 [8]) | status (u32, padded to 8) | final_flow
+        (u32 [n]) | final_csum (u16 [n]) | final_frames (u8 [n * H]) | order
+        (u32 [n]) | order_off (u32 [n + 1]) | valid (u8 [n]); then the size.
+        flow_info to final_frames is what the host reads, in one copy."""
+        lay, at = {}, 0
+        for name, nbytes in (("pointer", 8 * n), ("flow_info", 64 * n), ("info", 64), ("status", 8),
+                             ("final_flow", 4 * n), ("final_csum", 2 * n), ("final_frames", n * H)):
+            lay[name] = at
+            at += nbytes
+        lay["host_end"] = at
+        at = (at + 3) & ~3
+        for name, nbytes in (("order", 4 * n), ("order_off", 4 * (n + 1)), ("valid", n)):
+            lay[name] = at
+            at += nbytes
+        lay["size"] = at
+        return lay
+
+    def _cut(self, name, nbytes, dtype):
+        v = self._views.get(name)
+        if v is None:
+            lo = self._lay[name]
+            v = self._buf[lo:lo + nbytes]
+            v = self._views[name] = v if dtype is None else v.view(dtype)
+        return v
+
+    valid = property(lambda self: self._cut("valid", self._n, None))
+
+    @property
+    def pointer(self):
+        import torch
+        return self._cut("pointer", 8 * self._n, torch.int64)
+
+    @property
+    def order(self):
+        import torch
+        return self._cut("order", 4 * self._n, torch.int32)
+
+    @property
+    def order_off(self):
+        import torch
+        return self._cut("order_off", 4 * (self._n + 1), torch.int32)
+
+    @property
+    def flow_info(self):
+        import torch
+        return self._cut("flow_info", 64 * self._n, torch.int64).view(self._n, 8)
+
+    @property
+    def info(self):
+        import torch
+        return self._cut("info", 64, torch.int64)
+
+    @property
+    def status(self):
+        import torch
+        return self._cut("status", 4, torch.int32)
+
+    @property
+    def final_frames(self):
+        return self._cut("final_frames", self._n * self._H, None).view(self._n, self._H)
+
+    @property
+    def final_csum(self):
+        import torch
+        return self._cut("final_csum", 2 * self._n, torch.uint16)
+
+    @property
+    def final_flow(self):
+        import torch
+        return self._cut("final_flow", 4 * self._n, torch.int32)
+
+    def _read(self):
+        if self._host is None:
+            lay, n, H = self._lay, self._n, self._H
+            lo = lay["flow_info"]
+            raw = self._buf[lo:lay["host_end"]].cpu().numpy()
+            words = raw[:lay["status"] + 8 - lo].view(np.int64)
+            info = [int(v) for v in words[8 * n:8 * n + 8]]
+            A, E = info[0], info[2] if H else 0
+            flows = words[:8 * A].reshape(A, 8).copy()
+            fflow = raw[lay["final_flow"] - lo:lay["final_flow"] - lo + 4 * E].view(np.int32).copy()
+            at = lay["final_frames"] - lo
+            frames = [raw[at + H * e:at + H * (e + 1)].tobytes() for e in range(E)]
+            self._host = (info, flows, int(words[8 * n + 8]) & 0xFFFFFFFF, fflow, frames)
+        return self._host
+
+    active = property(lambda self: self._read()[0][0])
+    count = property(lambda self: self._read()[0][1])
+    ended = property(lambda self: self._read()[0][2])
+    newly_acknowledged = property(lambda self: self._read()[0][3])
+    flowless = property(lambda self: self._read()[0][4])
+
+    def flows(self):
+        """int64 [A, 8] on the host, ascending by slot: slot, end, valid
+        replies, characters newly acknowledged, p after, next frame, done,
+        closing_seq | closing_ack << 16 of every active flow."""
+        return self._read()[1]
+
+    def finals(self):
+        """[(a, datagram bytes)] of the flows that ended in this call, a the row
+        of ``flows()``; empty without a ``final_layout``."""
+        h = self._read()
+        return list(zip(h[3].tolist(), h[4]))
+
+    def check(self) -> "AckFlows":
+        _raise_bits(self._read()[2], _ST_ACK_FLOWS)
+        return self
+
+    def __len__(self) -> int:
+        return self._n
+
+
+def _ack_flows_args(flow, states, mode, final_layout, dev, n):
+    import torch
+    _flows_tensor(flow, "flow", dev, (torch.int32,), n)
+    _flows_tensor(states, "states", dev, (torch.int64,), ndim=2)
+    if states.shape[1] != 8 or not 1 <= states.shape[0] <= 0xFFFFFFFE:
+        raise ValueError(f"states must be int64 [n_flows, 8] with 1 <= n_flows <= 2^32 - 2, got {tuple(states.shape)}")
+    try:
+        m = ACK_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"mode must be 'exact' or 'cumulative', got {mode!r}") from None
+    H = 0 if final_layout is None else layout_header_len(final_layout)
+    return m, H
+
+
+def ack_flows(seq, ack, flags, flow, *, states, usable=None, mode: str = "exact", final_layout=None,
+              stream=None) -> AckFlows:
+    """``ack_progress`` for a batch that carries the replies of many transfers
+    (rudp_ack_flows; include/rudp.h states the rule): ``flow`` (int32 [N]
+    holding u32 values) names each reply's row in ``states`` (int64 [n_flows,
+    8] from ``ack_flow_states``, rows opened with ``ack_flow_open``; words 0 to
+    3 are updated in place), -1 (``FLOW_NONE``) a reply to ignore.  Every flow
+    is judged by the sender's rule on its own replies in arrival order, all
+    flows in one launch.  ``final_layout`` ("rudp5" / "rudp7"): also build the
+    closing datagram of every flow that ended.  At most ``FLOWS_MAX_BATCH``
+    replies.  Never waits; ``check()`` on the result raises when a slot was out
+    of range or a row refused."""
+    for name, t in (("seq", seq), ("ack", ack), ("flags", flags), ("flow", flow), ("states", states)):
+        if not _is_torch(t):
+            raise TypeError(f"ack_flows takes torch tensors on a HIP device (no host-memory form): {name}")
+    import torch
+    dev = seq.device
+    if dev.type != "cuda":
+        raise ValueError("ack_flows runs on a HIP device")
+    _flows_tensor(seq, "seq", dev, (torch.uint16,))
+    n = seq.shape[0]
+    if n > FLOWS_MAX_BATCH:
+        raise ValueError(f"ack_flows takes at most {FLOWS_MAX_BATCH} replies (one recvmmsg batch), got {n}")
+    _flows_tensor(ack, "ack", dev, (torch.uint16,), n)
+    _flows_tensor(flags, "flags", dev, (torch.uint8,), n)
+    if usable is not None:
+        _flows_tensor(usable, "usable", dev, (torch.uint8, torch.bool), n)
+    m, H = _ack_flows_args(flow, states, mode, final_layout, dev, n)
+    lay = AckFlows.layout(n, H)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        buf = torch.empty(lay["size"], dtype=torch.uint8, device=dev)
+    base = buf.data_ptr()
+
+    def tab(t):
+        return t if n else None
+
+    _native.check(_native.lib().rudp_ack_flows(
+        tab(seq.data_ptr()), tab(ack.data_ptr()), tab(flags.data_ptr()),
+        usable.data_ptr() if usable is not None and n else None, tab(flow.data_ptr()), n, m, states.data_ptr(),
+        states.shape[0], tab(base + lay["valid"]), tab(base + lay["pointer"]), tab(base + lay["order"]),
+        tab(base + lay["order_off"]), tab(base + lay["flow_info"]), base + lay["info"], base + lay["status"], H,
+        tab(base + lay["final_frames"]) if H else None, tab(base + lay["final_csum"]) if H else None,
+        tab(base + lay["final_flow"]) if H else None, dev.index or 0, _stream_ptr(stream, dev)))
+    return AckFlows(buf, n, H, states)
+
+
+class AcknowledgedFlows(NamedTuple):
+    """Result of ``acknowledge_flows``: ``decoded`` (``VarlenDecoded``: seq, ack,
+    flags, ok), ``usable`` (u8 [N]) and ``judged`` (``AckFlows``)."""
+    decoded: Any
+    usable: Any
+    judged: AckFlows
+
+
+def acknowledge_flows(frames, frame_off, flow, layout: Union[str, int] = "rudp7", *, states, csum=None,
+                      mode: str = "exact", stream=None) -> AcknowledgedFlows:
+    """Reply datagrams of many transfers (packed frames, as recvmmsg leaves
+    them) to every sender's new state and the closing datagrams of the flows
+    that ended: ``unpack_batch_varlen`` without a host check, ``acknowledge``'s
+    usable rule (the checksum and the frame's shape are good) and ``ack_flows``
+    with ``final_layout=layout``, chained on the stream with no host wait.  A
+    frame with bad offsets is unusable and sets RUDP_ST_OFFSETS in
+    ``decoded.status``."""
+    H = layout_header_len(layout)
+    if not _is_torch(frames) or not _is_torch(frame_off) or not _is_torch(flow) or not _is_torch(states):
+        raise TypeError("acknowledge_flows takes torch tensors on a HIP device (no host-memory form)")
+    import torch
+    dev = frames.device
+    if dev.type != "cuda":
+        raise ValueError("acknowledge_flows runs on a HIP device")
+    n = frame_off.shape[0] - 1 if frame_off.dim() == 1 else -1
+    if n < 0:
+        raise ValueError("frame_off needs N + 1 entries")
+    if n > FLOWS_MAX_BATCH:
+        raise ValueError(f"acknowledge_flows takes at most {FLOWS_MAX_BATCH} replies (one recvmmsg batch), got {n}")
+    _ack_flows_args(flow, states, mode, layout, dev, n)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        dec = unpack_batch_varlen(frames, frame_off, H, csum=csum, check=False, stream=stream)
+        usable = (dec.ok == _native.OK_GOOD) | (dec.ok == _native.OK_UNVERIFIED)
+        usable = usable.to(torch.uint8)
+    judged = ack_flows(dec.seq, dec.ack, dec.flags, flow, states=states, usable=usable, mode=mode,
+                       final_layout=layout, stream=stream)
+    return AcknowledgedFlows(dec, usable, judged)
+
+
 # ------------------------------------------------------------ message -> datagrams
 MAX_CHUNK = 16383  # characters per datagram: 4 * 16383 <= 65535 payload bytes
 

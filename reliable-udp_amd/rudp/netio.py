@@ -448,3 +448,44 @@ class BatchReceiver:
         for t in (d_frames, d_off, res._buf):  # the result's members are views of one buffer
             t.record_stream(cur)
         return res, d_frames, d_off
+
+    def acknowledge_flows(self, flow, layout="rudp5", *, states, mode="exact", csum=None, stream=None):
+        """H2D of the received reply datagrams as ``receive()`` does it (the same
+        slot and event bookkeeping) and of ``flow`` (numpy u32 [count]: each
+        reply's slot in ``states``, from ``flows.FlowTable.lookup(self.sources)``),
+        then ``batch.acknowledge_flows``: the batch judged for all the sends it
+        answers at once, with the closing datagrams of the flows that ended.
+        Never waits for the device.
+
+        Returns ``(AcknowledgedFlows, d_frames, d_frame_off)``; closing datagram
+        e goes to the peer of slot ``res.judged.flows()[a][0]`` for ``(a,
+        frame) = res.judged.finals()[e]``."""
+        import torch
+        s = stream if stream is not None else self.stream
+        k, n = self._slot, self.count
+        if k < 0:
+            raise RuntimeError("acknowledge_flows() before any recv()")
+        flow = np.ascontiguousarray(flow, dtype=np.uint32)
+        if flow.shape != (n,):
+            raise ValueError(f"flow has shape {flow.shape} for {n} datagrams")
+        total = int(self._off_t[k][n])
+        h_flow = torch.from_numpy(flow.view(np.int32)).pin_memory()
+        s.wait_stream(torch.cuda.current_stream(self.device))  # e.g. states rows written by the caller
+        with torch.cuda.stream(s):
+            d_frames = torch.empty((total,), dtype=torch.uint8, device=self.device)
+            d_off = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+            d_flow = torch.empty((n,), dtype=torch.int32, device=self.device)
+            d_frames.copy_(self._frames_t[k][:total], non_blocking=True)
+            d_off.copy_(self._off_t[k][:n + 1], non_blocking=True)
+            d_flow.copy_(h_flow, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(s)
+            self._copied[k] = ev
+            res = _batch.acknowledge_flows(d_frames, d_off, d_flow, layout, states=states, csum=csum, mode=mode,
+                                           stream=s)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(s)
+        # allocated on `s`, used on the caller's stream from here on
+        for t in (d_frames, d_off, d_flow, res.decoded._buf, res.usable, res.judged._buf):
+            t.record_stream(cur)
+        return res, d_frames, d_off

@@ -54,6 +54,7 @@ MAX_DATAGRAM = 1024   # recvfrom size of the reference (utils/reliableUDP.py:9)
 MAX_SENDS = 20        # sends without progress before giving up (:10)
 CHUNK = 1             # characters per datagram (:11)
 FIN_WAIT_S = 0.5      # receiver's wait for the final ACK (:166)
+FLOW_LINGER_S = 1.0   # flows.FlowSender: an ended flow keeps its slot this long to repeat its closing ACK
 
 
 class Reply(NamedTuple):
